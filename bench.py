@@ -9,11 +9,13 @@ instead: strong scaling, BASELINE.json configs[2] with T = 100000).  Loci are in
 collective; the one exchange of the design -- the gather of the fixed-size posterior records of every rank (RCCL
 all_gather over xGMI) -- is inside the timed region and reported as gather_ms.
 
-Besides the headline line the JSON carries `value_incl_h2d` (the same pass fed from host memory with the compact int8 /
-int16 input and the posterior records copied back: what a caller gets end to end) and, under `extra`, the other
-single-GPU configurations of BASELINE.json: config4 (call-exact, hexaploid, 16 haplotypes, 500 reads) and config5
-(octoploid, 20 SNVs, 1000 reads, 4 chains x 2000 steps), each with its kernel time, a roofline figure that means
-something for it, and the oracle's CPU rate.
+A plain run sets up, warms up, times --steps passes and prints the headline line.  With --full the JSON also carries
+`value_one_in_flight` and `roofline` (passes run one at a time after the timed region), the cross-rank record check,
+`value_incl_h2d` (the same pass fed from host memory with the compact int8 / int16 input and the posterior records copied
+back: what a caller gets end to end), `cpu_baseline` and, under `extra`, the other single-GPU configurations of
+BASELINE.json: config4 (call-exact, hexaploid, 16 haplotypes, 500 reads) and config5 (octoploid, 20 SNVs, 1000 reads,
+4 chains x 2000 steps), each with its kernel time, a roofline figure that means something for it, and the oracle's CPU rate.
+--dump-outputs DIR writes what the last timed pass computed (dump_outputs) so that two builds can be compared.
 
 Prints ONE JSON line (rank 0).  See DESIGN.md "Measurement" for how roofline / cpu_baseline are defined.
 """
@@ -79,6 +81,12 @@ def parse():
     ap.add_argument("--tempered", action="store_true",
                     help="also run extra.config5_tempered (one chain x 4 temperatures at configs[4]'s shape): minutes of GPU time, "
                          "so not part of the default line (profiles/ holds the measured run)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: value_one_in_flight and roofline (passes one at a time after the timed "
+                         "region), the agreement of the passes in flight, the cross-rank record check and gather_ms, value_incl_h2d, "
+                         "extra and cpu_baseline (--no-extras / --no-cpu-baseline / --tempered select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed pass computed (rank 0's loci) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -943,6 +951,76 @@ def bench_program_e2e(args):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def headline(args, U, n_total, world, n_dev, nfl, backend, dt):
+    """The result line of a plain run: loci/s over the timed passes and the configuration they ran."""
+    return {
+        "metric": "loci/sec (whole node) for 1000-step MCMC, tetraploid 8-SNV loci, 1/2/4/8 GPUs",
+        "value": n_total * args.steps / dt,
+        "unit": "loci/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if args.total_loci else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": "%d synthetic tetraploid loci per GPU, %d SNVs, %d reads, %d MCMC steps x %d chains, burn %d, "
+                        "posterior summary (BASELINE.json configs[1]); %d passes in flight on separate HIP streams, each with its own "
+                        "device buffers" % (U, args.snvs, args.reads, args.mcmc_steps, args.chains, args.burn, nfl),
+            "loci_per_gpu": U, "ploidy": args.ploidy, "snvs": args.snvs, "reads": args.reads,
+            "mcmc_steps": args.mcmc_steps, "chains": args.chains, "burn": args.burn,
+            "llk_cache": not args.no_cache, "passes_in_flight": nfl,
+            "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
+            "parallelism": "loci sharded contiguously over %d rank(s) on %d device(s); posterior records all-gathered every pass%s"
+                           % (world, min(world, n_dev), "" if backend is None else " (%s)" % ("RCCL" if backend == "nccl" else backend)),
+            "world_size": world, "devices": min(world, n_dev), "backend": backend,
+        },
+    }
+
+
+def dump_outputs(b, out_dir, budget=64 << 20):
+    """--dump-outputs: what the timed pass hands its caller, from batch b after its last pass, as out_dir/<name>.npy --
+    every unit's posterior summary (mode genotype as alleles [U, K, M], SPM and GPM, distinct genotypes after burn-in, count
+    of the mode genotype) and the raw traces (alleles [n, C, S, K, M] and log-likelihoods [n, C, S]) of a few units.  Alleles
+    are float32, everything else float64.  The files stay under `budget` bytes: beyond it the units are a fixed, seeded
+    sample (units.npy / trace_units.npy hold their indices)."""
+    import torch
+    from mchap_amd.assemble import unpack_trace
+
+    U, R, M, A = b.shape
+    K, Cn, S = b.K, b.Cn, b.S
+    post = b.posterior_host()
+    fixed = b.d_fixed.view(U, M).cpu().numpy()
+    rng = np.random.default_rng(0)
+
+    def sample(n):
+        return np.arange(U) if n >= U else np.sort(rng.choice(U, n, replace=False))
+
+    half = budget // 2 - 4096  # (room for the .npy headers)
+    units = sample(half // (K * M * 4 + 40))
+    tunits = sample(min(64, half // (Cn * S * (K * M * 4 + 8) + 8)))
+    idx = torch.from_numpy(tunits).to(b.d_trace.device)
+    words = b.d_trace.view(U, Cn, S, K)[idx].cpu().numpy().view(np.uint64)
+    llks = b.d_llks.view(U, Cn, S)[idx].cpu().numpy()
+    arrays = {
+        "units": units.astype(np.float64),
+        "mode_genotype": np.stack([unpack_trace(post["mode_words"][u], fixed[u], A) for u in units]).astype(np.float32),
+        "spm_gpm": post["stats"][units].astype(np.float64),
+        "n_genotypes": post["n"][units].astype(np.float64),
+        "mode_count": post["mode_count"][units].astype(np.float64),
+        "trace_units": tunits.astype(np.float64),
+        "trace_genotypes": np.stack([unpack_trace(words[i], fixed[u], A) for i, u in enumerate(tunits)]).astype(np.float32)
+        if len(tunits) else np.zeros((0, Cn, S, K, M), np.float32),
+        "trace_llks": llks.astype(np.float64),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` without a launcher around it (the reference deals its loci to a pool of worker processes the same
     way: application/baseclass.py:360-388): start N fresh rank processes -- this parent has not imported torch nor made any HIP
@@ -1076,6 +1154,20 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    for b in batches:
+        status = b.d_status.cpu().numpy()
+        if (status > 1).any() or (status < 0).any():
+            raise SystemExit("sampler reported errors: %s" % np.unique(status))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(batches[(args.steps - 1) % nfl], args.dump_outputs)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, U, n_total, world, n_dev, nfl, backend, dt)))
+        if dist is not None:
+            barrier()
+            dist.destroy_process_group()
+        return
+
     # The kernel's own launch duration (roofline): one pass in flight, HIP events on the launch stream right around
     # the sampler's launches -- with several passes in flight those spans overlap and say nothing about the kernel
     batches[0].time_sampler(True)  # (per-call events, owned by this batch: nothing process-wide)
@@ -1094,10 +1186,6 @@ def main():
     kern_ms = float(np.mean(kernel_ms))
     kern_name = batches[0].sampler_name
 
-    for b in batches:
-        status = b.d_status.cpu().numpy()
-        if (status > 1).any() or (status < 0).any():
-            raise SystemExit("sampler reported errors: %s" % np.unique(status))
     for b in batches[1:]:  # every batch in flight produced the same traces
         if not (torch.equal(b.d_trace, batch.d_trace) and torch.equal(b.post["mode_words"], batch.post["mode_words"])):
             raise SystemExit("passes in flight disagree")
@@ -1120,8 +1208,6 @@ def main():
         gather_checked = n_chk
 
     if rank == 0:
-        total_units = n_total * args.steps
-        value = total_units / dt
         # algorithmic HBM bytes per locus: float64 read tensor in, packed trace + llk out
         bytes_in = args.reads * args.snvs * 2 * 8
         bytes_out = args.chains * args.mcmc_steps * (args.ploidy * 8 + 8)
@@ -1134,31 +1220,8 @@ def main():
         w = valu_issue_cycles(sq)
         valu_insts = float(sq["SQ_INSTS_VALU"]) if w else None
         valu_frac = (w["cycles"] / (kern_ms * 1e-3) / SIMD_CYCLES_PER_S) if w else None
-        out = {
-            "metric": "loci/sec (whole node) for 1000-step MCMC, tetraploid 8-SNV loci, 1/2/4/8 GPUs",
-            "value": value,
-            "unit": "loci/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong" if args.total_loci else "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": "%d synthetic tetraploid loci per GPU, %d SNVs, %d reads, %d MCMC steps x %d chains, burn %d, "
-                            "posterior summary (BASELINE.json configs[1]); %d passes in flight on separate HIP streams, each with its own "
-                            "device buffers" % (U, args.snvs, args.reads, args.mcmc_steps, args.chains, args.burn, nfl),
-                "loci_per_gpu": U, "ploidy": args.ploidy, "snvs": args.snvs, "reads": args.reads,
-                "mcmc_steps": args.mcmc_steps, "chains": args.chains, "burn": args.burn,
-                "llk_cache": not args.no_cache, "passes_in_flight": nfl,
-                "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
-                "parallelism": "loci sharded contiguously over %d rank(s) on %d device(s); posterior records all-gathered every pass%s"
-                               % (world, min(world, n_dev), "" if backend is None else " (%s)" % ("RCCL" if backend == "nccl" else backend)),
-                "world_size": world, "devices": min(world, n_dev), "backend": backend,
-            },
+        out = headline(args, U, n_total, world, n_dev, nfl, backend, dt)
+        out.update({
             "roofline": {
                 "bound": "hbm", "kernel": kern_name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS, "traffic": (prof or {}).get("hbm_bytes_per_launch"),
@@ -1176,7 +1239,7 @@ def main():
                         "likelihood evaluations at two waves per SIMD (first phase) and Philox throughput (coasting), not by "
                         "HBM: the HBM fraction is reported because the contract asks for it",
             },
-        }
+        })
         if dist is None:
             out["value_one_in_flight"] = U * n_iso / dt_iso
         if dist is not None:

@@ -46,7 +46,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, MCHAP_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--loci", "512", "--no-cpu-baseline"]
+           "--loci", "512", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -65,7 +65,7 @@ def test_bench_strong_scaling_uneven_shards():
     env = dict(os.environ, MCHAP_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29534", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--total-loci", "777", "--no-cpu-baseline"]
+           "--total-loci", "777", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
@@ -79,7 +79,7 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     the GPU and relays rank 0's line (round 3's flag was parsed and ignored: one rank, n_gpus 1).  On a box with fewer GPUs than
     ranks the ranks share the device and gloo carries the gather; with a GPU each it is RCCL -- the line says which."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MCHAP_BENCH_BACKEND")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--loci", "512", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--loci", "512", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -104,7 +104,7 @@ def test_bench_single_rank_over_rccl():
     env.update(MCHAP_BENCH_DIST="1", MCHAP_BENCH_BACKEND="nccl", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541", RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--loci", "1024", "--inflight", "4",
-           "--no-cpu-baseline", "--no-extras"]
+           "--no-cpu-baseline", "--no-extras", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
@@ -118,7 +118,7 @@ def test_bench_config3_at_its_size_eight_ranks_on_one_gpu():
     pass, the ranks sharing the one device there is (gloo carries the gather), the cross-rank record check on."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MCHAP_BENCH_BACKEND")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--total-loci", "100000", "--inflight", "1", "--steps", "1",
-           "--warmup", "0", "--no-cpu-baseline", "--no-extras"]
+           "--warmup", "0", "--no-cpu-baseline", "--no-extras", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1800, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
