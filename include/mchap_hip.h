@@ -413,6 +413,28 @@ int mchap_bam_columns(const uint8_t *buf, int64_t n, int64_t start, int64_t n_re
                       int64_t *seq_off, int64_t *qual_off, int64_t *rg, int64_t *qname_id, int64_t *seg_first,
                       int64_t *c_rec, int64_t *c_op, int64_t *c_len, int64_t *c_ref0, int64_t *c_read0);
 
+/* find-snvs pileup (reference application/find_snvs.py bam_region_depths / write_vcf_block; mchap_amd/find_snvs.py builds the
+ * tables).  `bytes[0 .. n_bytes)`: the alignment records of a block, per sample one contiguous run, on the device; every offset
+ * below indexes it (a sequence position as a nibble index: 2 x byte offset of the packed sequence + read offset).
+ * mchap_pileup_overlap_device: htslib's mate-overlap rule on the quality bytes, in place.  segments [n_segments][4] int64 =
+ *   {first mate's sequence nibble, second mate's sequence nibble, first mate's quality byte, second mate's quality byte} of a run
+ *   of reference positions both mates align a base to; first [n_segments + 1] = the run's first position among n_positions.
+ *   Equal bases: first q = min(q1 + q2, 200), second q = 0; else the higher (first on a tie) keeps (uint8)(0.8 q), the other 0.
+ * mchap_pileup_depth_device: depth [n_rows][n_samples][4] int32 (A C G T) of the bases with quality >= min_base_quality.
+ *   segments [*][4] int64 = {row, length, sequence nibble, quality byte} of an aligned run of one read, clipped to one target and
+ *   one tile of `tile` (1..2048) rows; tile_first [n_samples x n_tiles + 1] = the CSR index of the segments of (sample, tile).
+ *   variant 0: LDS histogram per (sample, tile), every row written; 1 (measurement): global atomics into a zeroed `depth`.
+ * mchap_pileup_filter_device: per row, the reference's allele filter (maf, mad, ind_maf, ind_mad, min_ind) over `depth`;
+ *   ref_index [n_rows] int8 (0-3, -1: not ACGT).  flags [n_rows]: bit 0 = a record, bits 1-4 = kept alleles, bits 8-15 = VCF
+ *   order of the alleles (2 bits each, reference first), bit 16 = REFMASKED; admf [n_rows][4] float64 by allele index. */
+int mchap_pileup_overlap_device(uint8_t *bytes, int64_t n_bytes, const int64_t *segments, const int64_t *first, int64_t n_segments,
+                                int64_t n_positions, void *stream);
+int mchap_pileup_depth_device(const uint8_t *bytes, int64_t n_bytes, const int64_t *segments, const int64_t *tile_first,
+                              int n_samples, int64_t n_rows, int tile, int min_base_quality, int variant, int32_t *depth,
+                              void *stream);
+int mchap_pileup_filter_device(const int32_t *depth, const int8_t *ref_index, int64_t n_rows, int n_samples, double maf, int64_t mad,
+                               double ind_maf, int64_t ind_mad, int64_t min_ind, int32_t *flags, double *admf, void *stream);
+
 /* Introspection */
 const char *mchap_version(void);
 const char *mchap_last_error(void);

@@ -201,6 +201,11 @@ def lib():
         L.mchap_bam_count.restype = C.c_int64
         L.mchap_bam_count.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
         L.mchap_bam_columns.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_char_p, C.c_int] + [C.c_void_p] * 16
+        L.mchap_pileup_overlap_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        L.mchap_pileup_depth_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                                C.c_int, C.c_void_p, C.c_void_p]
+        L.mchap_pileup_filter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_int64, C.c_double,
+                                                 C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mchap_timer_ms.argtypes = [C.c_void_p]
         L.mchap_timer_destroy.argtypes = [C.c_void_p]
         _libs[path] = L
@@ -242,6 +247,9 @@ def sampler_name(cfg, units_host):
 EXPORTS = [
     "mchap_bam_count",
     "mchap_bam_columns",
+    "mchap_pileup_overlap_device",
+    "mchap_pileup_depth_device",
+    "mchap_pileup_filter_device",
     "mchap_denovo_fit_batch_device",
     "mchap_denovo_fit_batch_calls_device",
     "mchap_denovo_fit_batch",

@@ -1,4 +1,4 @@
-"""Command line of the programs built on the kernels: `python -m mchap_amd {assemble,call,call-exact} ...` with the
+"""Command line of the programs built on the kernels: `python -m mchap_amd {assemble,call,call-exact,find-snvs} ...` with the
 reference's flag names, defaults and meaning (application/cli.py:14-60; application/arguments.py: the argument tables
 ASSEMBLE_MCMC_PARSER_ARGUMENTS / CALL_EXACT_PARSER_ARGUMENTS / CALL_MCMC_PARSER_ARGUMENTS and the collect_* functions)
 for these three programs: every flag those tables define is accepted here with the same arity and default.  Output: a VCF
@@ -14,7 +14,7 @@ import sys
 
 from . import __version__
 
-PROGRAMS = ("assemble", "call", "call-exact")
+PROGRAMS = ("assemble", "call", "call-exact", "find-snvs")
 
 
 def _flag(p, name, dest, action, help):
@@ -56,6 +56,24 @@ def _mcmc_args(p):
 def build_parser(program):
     """The parser of one program: the flags of the reference's argument table for it (application/arguments.py:742-838)."""
     p = argparse.ArgumentParser("mchap_amd " + program)
+    if program == "find-snvs":
+        # (reference application/find_snvs.py main: its argument list; --cores as the other programs have it)
+        p.add_argument("--targets", type=str, nargs=1, default=[None], help="BED file (3+ columns) of the intervals to search")
+        p.add_argument("--reference", type=str, nargs=1, default=[None], help="reference FASTA")
+        p.add_argument("--bam", type=str, nargs="+", default=[],
+                       help="BAM / SAM file(s), a text file with one path per line, or a text file of sample<TAB>path lines")
+        p.add_argument("--maf", type=float, nargs=1, default=[0.0], help="minimum mean of the samples' allele frequencies")
+        p.add_argument("--mad", type=int, nargs=1, default=[0], help="minimum allele depth summed over the samples")
+        p.add_argument("--ind-maf", type=float, nargs=1, default=[0.1], help="minimum allele frequency within a sample")
+        p.add_argument("--ind-mad", type=int, nargs=1, default=[3], help="minimum allele depth within a sample")
+        p.add_argument("--min-ind", type=int, nargs=1, default=[1], help="samples that must meet --ind-maf and --ind-mad")
+        p.add_argument("--read-group-field", type=str, nargs=1, default=["SM"], help='read-group field used as the sample id: "SM" or "ID"')
+        p.add_argument("--mapping-quality", type=int, nargs=1, default=[20], help="minimum mapping quality of the reads counted")
+        _flag(p, "--keep-duplicate-reads", "skip_duplicates", "store_false", "count reads marked as duplicates")
+        _flag(p, "--keep-qcfail-reads", "skip_qcfail", "store_false", "count reads marked as qcfail")
+        _flag(p, "--keep-supplementary-reads", "skip_supplementary", "store_false", "count reads marked as supplementary")
+        p.add_argument("--cores", type=int, nargs=1, default=[1], help="host threads reading the alignment files")
+        return p
     if program == "assemble":
         _sample_args(p, 1)
         p.add_argument("--reference", type=str, nargs=1, default=[None], help="reference FASTA")
@@ -119,6 +137,8 @@ def run(argv, out=None):
     out = out or sys.stdout
     program = argv[1]
     args = build_parser(program).parse_args(argv[2:])
+    if program == "find-snvs":
+        return _run_find_snvs(argv, args, out)
     # must have some source of error in reads (application/arguments.py:1190-1195)
     if args.ignore_base_phred_scores and args.base_error_rate[0] == 0.0:
         raise ValueError("Cannot ignore base phred scores if --base-error-rate is 0")
@@ -191,6 +211,36 @@ def run(argv, out=None):
         if program == "assemble" and line.split("\t", 7)[6] == "LIMIT":
             run.limit_records += 1  # (a target beyond the build's shape limits: written with null genotypes, and main() says so)
     return n
+
+
+def _run_find_snvs(argv, args, out):
+    """find-snvs: the header, then the records of every BED interval in file order (one process: sharding is out of scope)."""
+    import os
+
+    from . import application, find_snvs, io, vcfheader
+
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("find-snvs runs as a single process: it does not shard over several ranks (WORLD_SIZE > 1)")
+    if args.targets[0] is None or args.reference[0] is None:
+        raise ValueError("--targets and --reference are required")
+    id_field = args.read_group_field[0]
+    if id_field not in ("SM", "ID"):
+        raise ValueError('--read-group-field must be "SM" or "ID"')
+    sample_bams = io.sample_bam_table(args.bam, id_field)
+    find_snvs.check_one_sample_per_file(sample_bams, id_field)
+    reference = io.Reference(args.reference[0])
+    targets = find_snvs.read_targets(args.targets[0])
+    source = application.ReadSource(sample_bams, read_group_field=id_field, mapping_quality=args.mapping_quality[0],
+                                    skip_duplicates=args.skip_duplicates, skip_qcfail=args.skip_qcfail,
+                                    skip_supplementary=args.skip_supplementary, workers=args.cores[0])
+    records = find_snvs.find_snvs(targets, reference, source, maf=args.maf[0], mad=args.mad[0], ind_maf=args.ind_maf[0],
+                                  ind_mad=args.ind_mad[0], min_ind=args.min_ind[0])
+    lines = list(records)  # (errors -- an interval past its contig's end -- surface before any output)
+    for line in vcfheader.find_snvs_header_lines(["mchap_amd"] + list(argv[1:]), args.reference[0], list(sample_bams), reference.contigs):
+        out.write(line + "\n")
+    for line in lines:
+        out.write(line + "\n")
+    return len(lines)
 
 
 def main(argv=None):

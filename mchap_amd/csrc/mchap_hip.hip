@@ -123,6 +123,15 @@ int fail(int code, const char *fmt, ...) {
   return code;
 }
 
+}  // namespace
+
+namespace mchap {
+// the error text of an entry point defined in another object of the library (pileup_inst.hip)
+int set_last_error(int code, const char *msg) { return fail(code, "%s", msg); }
+}  // namespace mchap
+
+namespace {
+
 #define HIP_TRY(expr)                                                                         \
   do {                                                                                        \
     hipError_t e_ = (expr);                                                                   \

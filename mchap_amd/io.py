@@ -770,6 +770,8 @@ class AlignmentColumns:
 
         block = field(0, "<i4")
         self.ref_id, self.pos = field(4, "<i4"), field(8, "<i4")
+        self.offsets = offs
+        self.next_ref_id, self.next_pos, self.tlen = field(24, "<i4"), field(28, "<i4"), field(32, "<i4")
         l_name, self.mapq = core[:, 12].astype(np.int64), core[:, 13].astype(np.int32)
         n_cig, self.flag, l_seq = field(16, "<u2").astype(np.int64), field(18, "<u2").astype(np.int32), field(20, "<i4").astype(np.int64)
         name_off = offs + 36
@@ -859,6 +861,10 @@ class AlignmentColumns:
             self.c_rec, self.c_op, self.c_len, self.c_ref0, self.c_read0)))
         if rc != 0:
             raise ValueError("malformed BAM record")
+        # mate fields (core bytes 24-35: next_refID, next_pos, tlen), read from the record offsets the walk found
+        self.offsets = offs
+        mate = b[offs[:, None] + np.arange(24, 36)] if n else np.zeros((0, 12), np.uint8)
+        self.next_ref_id, self.next_pos, self.tlen = (np.ascontiguousarray(mate[:, k:k + 4]).view("<i4").reshape(n) for k in (0, 4, 8))
         rid = np.where(self.ref_id < 0, np.int64(1) << 30, self.ref_id.astype(np.int64))  # unplaced reads sort last
         self.sort_key = (rid << 32) | self.pos.astype(np.int64).clip(0)
         self.sorted = bool(n < 2 or (self.sort_key[1:] >= self.sort_key[:-1]).all())
@@ -873,6 +879,45 @@ class AlignmentColumns:
         lo = int(np.searchsorted(self.sort_key, base | max(0, start - self.max_span), side="left"))
         hi = int(np.searchsorted(self.sort_key, base | max(0, stop), side="left"))
         return lo, hi
+
+
+def sam_columns(path, id_field="SM"):
+    """The records of a SAM text file as AlignmentColumns: each alignment line encoded as the BAM record it stands for (SAM
+    specification 4.2), so that SAM input enters the same tables as BAM input.  Mate fields: RNEXT (`=` is the read's own
+    reference, `*` none), PNEXT (1-based, 0 none) and TLEN."""
+    refs, rg = bam_header(path)
+    names = {n: i for i, (n, _) in enumerate(refs)}
+    code = {c: i for i, c in enumerate(SEQ_CODE)}
+    ops = {c: i for i, c in enumerate(CIGAR_OPS)}
+    out, offsets = bytearray(), []
+    for line in open(path):
+        if not line.strip() or line.startswith("@"):
+            continue
+        c = line.rstrip("\n").split("\t")
+        ref = names.get(c[2], -1)
+        nref = ref if c[6] == "=" else names.get(c[6], -1)
+        cigar = []
+        if c[5] != "*":
+            n = ""
+            for ch in c[5]:
+                if ch.isdigit():
+                    n += ch
+                else:
+                    cigar.append((int(n), ops[ch]))
+                    n = ""
+        seq = "" if c[9] == "*" else c[9]
+        packed = bytearray((len(seq) + 1) // 2)
+        for i, ch in enumerate(seq.upper()):
+            packed[i >> 1] |= code.get(ch, 15) << (4 if i % 2 == 0 else 0)
+        qual = bytes([255] * len(seq)) if c[10] == "*" else bytes(ord(q) - 33 for q in c[10])
+        tags = b"".join(b"RGZ" + t[5:].encode() + b"\0" for t in c[11:] if t.startswith("RG:Z:"))
+        name = c[0].encode() + b"\0"
+        body = struct.pack("<iiBBHHHiiii", ref, int(c[3]) - 1, len(name), int(c[4]), 0, len(cigar), int(c[1]), len(seq), nref,
+                           int(c[7]) - 1, int(c[8])) + name + b"".join(struct.pack("<I", (ln << 4) | op) for ln, op in cigar) + \
+            bytes(packed) + qual + tags
+        offsets.append(len(out))
+        out += struct.pack("<i", len(body)) + body
+    return AlignmentColumns(refs, rg, bytes(out), offsets, id_field)
 
 
 class BamFile:

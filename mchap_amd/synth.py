@@ -93,7 +93,8 @@ def _reg2bin(beg, end):
 def write_bam(path, contigs, read_groups, records, index=True):
     """Write a coordinate-sorted BAM file (BGZF) and, with index=True, its `.bai`.
     contigs: [(name, length)]; read_groups: {id: sample}; records: iterable of dicts with qname, flag, ref (contig index),
-    pos (0-based), mapq, cigar [(length, op char)], seq (str), qual (sequence of ints), rg (id), optionally tags_before (raw aux bytes).  Every record lies in one
+    pos (0-based), mapq, cigar [(length, op char)], seq (str), qual (sequence of ints), rg (id), optionally tags_before (raw aux bytes)
+    and the mate fields next_ref (contig index, default -1), next_pos (0-based, default -1) and tlen (default 0).  Every record lies in one
     BGZF block (a new block starts when the next record would not fit), so its virtual offsets are (block << 16 | offset)."""
     import struct
     import zlib
@@ -136,7 +137,8 @@ def write_bam(path, contigs, read_groups, records, index=True):
             tags = r["tags"]  # (the whole aux block as given, malformed ones included: tests)
         end = r["pos"] + max(ref_len, 1)
         b = _reg2bin(r["pos"], end)
-        body = struct.pack("<iiBBHHHiiii", r["ref"], r["pos"], len(name), r["mapq"], b, len(r["cigar"]), r["flag"], len(seq), -1, -1, 0) + \
+        body = struct.pack("<iiBBHHHiiii", r["ref"], r["pos"], len(name), r["mapq"], b, len(r["cigar"]), r["flag"], len(seq),
+                           r.get("next_ref", -1), r.get("next_pos", -1), r.get("tlen", 0)) + \
             name + cig + bytes(packed) + qual + tags
         rec = struct.pack("<i", len(body)) + body
         if len(cur) + len(rec) > 60000:
