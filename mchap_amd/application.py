@@ -262,6 +262,11 @@ def _run_exact_groups(units, ploidy_of, inbreeding_of, full, backend=None):
                 sub = _run_exact_groups(sub_units, ploidy_of, inbreeding_of, full, backend)
                 for (i, s), v in sub.items():
                     results[(keep[i], s)] = v
+                # (the chunk's units are copies: a LIMIT mark set on them belongs to the caller's records, else those records
+                # keep invalid None without results and the record formatter fails on them)
+                for i, ri in enumerate(keep):
+                    if sub_units[i].get("invalid") is not None and units[ri].get("invalid") is None:
+                        units[ri]["invalid"] = sub_units[i]["invalid"]
             continue
         U = len(members)
         reads = np.full((U, Rmax, M, A), np.nan)

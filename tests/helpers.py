@@ -42,3 +42,40 @@ def assert_same_posterior(got_genotypes, got_probs, exp_genotypes, exp_probs, rt
         b = sorted(g.tobytes() for g in exp_genotypes[i:j].astype(np.int8))
         assert a == b, (i, j)
         i = j
+
+
+def multiallelic_units(rng, U, K, H, n_alleles, R, qual=(5, 30), gap=0.15, window=None):
+    """Units of known haplotypes over SNVs of mixed allele counts, as `call-exact` meets them: reads [U, R, M, A] (A =
+    max(n_alleles)) encoded by encoding.as_probabilistic -- a called allele gets p, every other allele the position has
+    (1 - p) / 3, the alleles it lacks 0, a gap NaN except those ([nan, nan, 0] at a biallelic position of 3 alleles) --
+    and haplotypes int8 [U, H, M] with allele < n_alleles[j], distinct within a unit.  Reads come from a genotype of K
+    of the unit's haplotypes, with errors at rate 1 - p (another allele of the position) and gaps at rate `gap` or
+    outside a read window of `window` = (min, max) positions."""
+    from mchap_amd.encoding import as_probabilistic
+
+    na = np.asarray(n_alleles, dtype=int)
+    M, A = len(na), int(na.max())
+    reads = np.empty((U, R, M, A))
+    haps = np.zeros((U, H, M), np.int8)
+    for u in range(U):
+        if np.prod(na.astype(float)) <= 6 * H + 8:  # (few haplotypes exist: all of them)
+            pool = np.stack(np.meshgrid(*[np.arange(n) for n in na], indexing="ij"), axis=-1).reshape(-1, M).astype(np.int8)
+        else:
+            pool = np.unique(np.stack([rng.integers(0, na) for _ in range(6 * H + 8)]).astype(np.int8), axis=0)
+        assert len(pool) >= H, "too few distinct haplotypes for the allele counts"
+        rng.shuffle(pool)
+        haps[u] = pool[:H]
+        truth = haps[u][rng.integers(0, H, size=K)]
+        src = truth[rng.integers(0, K, size=R)]
+        q = rng.integers(qual[0], qual[1] + 1, size=src.shape)
+        p = (1.0 - 0.0024) * (1.0 - 10.0 ** (-q / 10.0))
+        other = (src + rng.integers(1, na, size=src.shape)) % na
+        calls = np.where(rng.random(src.shape) >= p, other, src).astype(np.int8)
+        calls[rng.random(src.shape) < gap] = -1
+        if window is not None:
+            wlen = rng.integers(min(window[0], M), min(window[1], M) + 1, size=R)
+            start = (rng.random(R) * (M - wlen + 1)).astype(int)
+            pos = np.arange(M)[None, :]
+            calls[(pos < start[:, None]) | (pos >= (start + wlen)[:, None])] = -1
+        reads[u] = as_probabilistic(calls, na, p)
+    return reads, haps

@@ -10,10 +10,16 @@ from oracle import binding as orc
 pytestmark = pytest.mark.gpu
 
 
-def _inputs(U, K, H, M, R, seed, qual=(5, 25)):
+def _inputs(U, K, H, M, R, seed, qual=(5, 25), n_alleles=None):
     from mchap_amd.synth import synth_units
 
     rng = np.random.default_rng(seed)
+    if n_alleles is not None:  # (SNVs of 2 to 4 alleles: reads [R, M, max(n_alleles)] as as_probabilistic encodes them)
+        from tests.helpers import multiallelic_units
+
+        assert len(n_alleles) == M
+        reads, haps = multiallelic_units(rng, U, K, H, n_alleles, R, qual=qual, window=(2, M))
+        return reads, haps, rng.integers(1, 4, size=(U, R)).astype(np.int64), rng
     reads, _, truth = synth_units(U, ploidy=K, n_pos=M, n_reads=R, first_unit=seed, window=(2, M), qual=qual)
     haps = np.zeros((U, H, M), np.int8)
     for u in range(U):
@@ -25,15 +31,19 @@ def _inputs(U, K, H, M, R, seed, qual=(5, 25)):
 
 
 @pytest.mark.parametrize("step_type", ["Gibbs", "Metropolis-Hastings"])
-@pytest.mark.parametrize("K,H,M,R", [(4, 6, 6, 40), (2, 9, 5, 20), (6, 5, 4, 70), (3, 12, 6, 130), (4, 18, 6, 1400),  # 202 KB of products per chain
-                                     (10, 6, 6, 50), (12, 5, 5, 90), (15, 4, 6, 40), (9, 7, 100, 60)],
+@pytest.mark.parametrize("K,H,M,R,na", [(4, 6, 6, 40, None), (2, 9, 5, 20, None), (6, 5, 4, 70, None), (3, 12, 6, 130, None),
+                                        (4, 18, 6, 1400, None),  # 202 KB of products per chain
+                                        (10, 6, 6, 50, None), (12, 5, 5, 90, None), (15, 4, 6, 40, None), (9, 7, 100, 60, None),
+                                        # tri- and tetra-allelic SNVs (haplotypes with allele < n_alleles[j], reads of A = 3 or 4)
+                                        (4, 8, 5, 60, [3] * 5), (6, 9, 6, 80, [2, 3, 4, 2, 4, 3]), (10, 6, 5, 50, [3, 2, 3, 3, 2])],
                          # (round 5: ploidies 9 to 15, and known haplotypes of 100 SNVs)
-                         ids=["K4", "K2", "K6", "K3", "tables-in-workspace", "K10", "K12", "K15", "K9-100snvs"])
-def test_traces_match_oracle_step_for_step(step_type, K, H, M, R):
+                         ids=["K4", "K2", "K6", "K3", "tables-in-workspace", "K10", "K12", "K15", "K9-100snvs", "K4-A3", "K6-A4", "K10-A3"])
+def test_traces_match_oracle_step_for_step(step_type, K, H, M, R, na):
     from mchap_amd.calling_mcmc import CallingMCMC
 
     U = 3
-    reads, haps, counts, rng = _inputs(U, K, H, M, R, seed=K * 100 + H)
+    reads, haps, counts, rng = _inputs(U, K, H, M, R, seed=K * 100 + H, n_alleles=na)
+    assert reads.shape[-1] == (2 if na is None else max(na))
     F = np.array([0.0, 0.12, 0.3])
     fr = rng.dirichlet(np.ones(H), size=U)
     st = 0 if step_type == "Gibbs" else 1

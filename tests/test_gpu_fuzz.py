@@ -41,3 +41,12 @@ def test_ragged_launches_match_oracle(seed):
     import fuzz_ragged
 
     assert fuzz_ragged.run(8, seed, verbose=True) == 0
+
+
+@pytest.mark.parametrize("seed", [51, 52, 53])
+def test_exact_caller_random_shapes_match_oracle(seed):
+    """The exact caller on random shapes (ploidy 1-15, 2-40 haplotypes, SNVs of 2-4 alleles, 1-2600 reads, read counts with
+    and without zeros, every prior): both forms' outputs against the oracle (tests/fuzz_exact.py)."""
+    import fuzz_exact
+
+    assert fuzz_exact.run(12, seed, verbose=True) == 0
