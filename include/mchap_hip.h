@@ -374,6 +374,18 @@ int64_t mchap_call_mcmc_workspace_bytes(int n_units, int n_haps, int ploidy, int
  * MCHAP_HIP_CALL_LANES (measurement): 0 = every chain on its own wavefront to the end, as before round 5; n = chains per
  * wavefront of call_coast_kernel.  The traces are the same either way. */
 int64_t mchap_call_mcmc_workspace_bytes_for(int n_units, int n_reads, int n_haps, int ploidy, int steps, int chains);
+/* Known haplotypes per unit.  Up to 256 the sampler above runs (call_mcmc_kernel: tables in LDS, Gibbs memo, coast hand-over).
+ * Beyond, up to mchap_call_mcmc_max_haps(ploidy) -- 0 for a ploidy out of range --, call_wide_kernel
+ * (csrc/call_wide_kernel.hpp) runs: the unit's product table P[r][h] and prior tables once per unit in the workspace
+ * (mchap_call_mcmc_workspace_bytes_for counts them), a sub-step's options over the lanes, every lane its own likelihood in the
+ * reference's order, no memo and no hand-over; the same results contract.  The bound is what the LDS holds of one chain's four
+ * option arrays; more haplotypes are MCHAP_ERR_LIMIT with a message naming it.  Apart from it the genotype-count rule holds as
+ * before: C(n_haps + ploidy - 1, ploidy) <= 2^62, else MCHAP_ERR_LIMIT (the table's keys are genotype ranks; 1024 haplotypes
+ * pass it up to ploidy 7, 806 do at ploidy 8).  Environment (measurement and tests; the traces do not depend on them):
+ * MCHAP_HIP_CALL_WIDE=1 runs call_wide_kernel whatever n_haps, MCHAP_HIP_CALL_WIDE_CHAINS=n puts at most n chains of a unit in
+ * a workgroup.  On this path one call takes at most 65535 units (MCHAP_ERR_LIMIT beyond: cut the batch, as `mchap call` does).
+ * Both functions above read MCHAP_HIP_CALL_WIDE too: size the workspace under the setting the call runs under. */
+int mchap_call_mcmc_max_haps(int ploidy);
 int mchap_call_mcmc_batch_device(int n_units, const double *reads, int n_reads, int n_pos, int max_allele,
                                  const int64_t *read_counts, const int8_t *haplotypes, int n_haps, int ploidy, int has_prior,
                                  const double *inbreeding, const double *frequencies, const int64_t *initial,

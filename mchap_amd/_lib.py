@@ -276,6 +276,7 @@ EXPORTS = [
     "mchap_exact_posterior_summaries",
     "mchap_call_mcmc_workspace_bytes",
     "mchap_call_mcmc_workspace_bytes_for",
+    "mchap_call_mcmc_max_haps",
     "mchap_call_mcmc_batch_device",
     "mchap_call_mcmc_batch",
     "mchap_version",

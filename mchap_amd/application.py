@@ -1462,7 +1462,8 @@ def call(vcf_path, sample_bams, ploidy=2, report=(), base_error_rate=0.0024, use
             # device bytes per unit: reads, traces, and the chains' tables of remembered likelihoods (the workspace)
             ws1 = int(_lib.lib().mchap_call_mcmc_workspace_bytes_for(1, Rmax, H, K, int(steps), int(chains)))
             per_unit = Rmax * M * A * 8 + Rmax * 8 + chains * steps * (K + 1) * 8 + ws1 + 4096
-            for members in _blocks(all_members, device_unit_budget(per_unit)):
+            # (at most 65535 units a call: the bound of the sampler over more than 256 haplotypes, include/mchap_hip.h)
+            for members in _blocks(all_members, min(65535, device_unit_budget(per_unit))):
                 U = len(members)
                 reads = np.full((U, Rmax, M, A), np.nan)
                 counts = np.zeros((U, Rmax), dtype=np.int64)

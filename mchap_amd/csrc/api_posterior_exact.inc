@@ -170,9 +170,10 @@ namespace {
 
 long long host_cwr(int n, int k) {
   if (n <= 0) return 0;
-  long long r = 1;
-  for (int d = 1; d <= k; d++) r = r * (n - 1 + d) / d;
-  return r;
+  // (the product before the division in 128 bits: it passes 2^63 for counts near 2^62, which cwr_fits admits)
+  unsigned __int128 r = 1;
+  for (int d = 1; d <= k; d++) r = r * (unsigned __int128)(n - 1 + d) / (unsigned __int128)d;
+  return (long long)r;
 }
 
 // C(n + k - 1, k) stays below 2^62 (the genotype indices and the call sampler's cache keys are int64; ploidy 15 over 200
@@ -557,7 +558,23 @@ int mchap_exact_posterior_mode_batch(int n_units, const double *reads, int n_rea
 }
 
 // ---- `mchap call`: sampler over known haplotypes ----
+// the path for many haplotypes (call_wide_kernel.hpp, its own object: call_wide_inst.hip)
+extern "C" int mchap_call_wide_max_haps(void);
+extern "C" int64_t mchap_call_wide_unit_bytes(int n_reads, int n_haps, int ploidy);
+extern "C" int mchap_call_wide_wg_chains(int n_haps, int chains, int forced);
+extern "C" int mchap_call_wide_launch(const mchap::CallParams *P, double *unit_tab, int wgc, hipStream_t stream);
+// more than CALL_MAX_HAPS known haplotypes, or MCHAP_HIP_CALL_WIDE=1 (measurement and tests: any number)
+static bool call_use_wide(int n_haps) {
+  if (n_haps > mchap::CALL_MAX_HAPS) return true;
+  const char *e = std::getenv("MCHAP_HIP_CALL_WIDE");
+  return e && std::atoi(e) == 1;
+}
+int mchap_call_mcmc_max_haps(int ploidy) {
+  if (ploidy < 1 || ploidy > MCHAP_MAX_PLOIDY_DENOVO) return 0;
+  return mchap_call_wide_max_haps();
+}
 static long long call_cache_slots(int n_haps, int ploidy, int steps) {
+  if (!cwr_fits(n_haps, ploidy)) return 64;  // (more than 2^62 genotypes: the call refuses the shape by name; nothing to size)
   const long long G = host_cwr(n_haps, ploidy);
   long long need = (long long)steps * ploidy * n_haps + (long long)ploidy * n_haps + 8;  // requests of a chain at most
   if (G < need) need = G;
@@ -582,6 +599,8 @@ static int64_t call_state_bytes(int n_units, int n_haps, int ploidy, int chains)
 int64_t mchap_call_mcmc_workspace_bytes_for(int n_units, int n_reads, int n_haps, int ploidy, int steps, int chains) {
   const int64_t base = mchap_call_mcmc_workspace_bytes(n_units, n_haps, ploidy, steps, chains);
   if (base == 0 || n_reads < 1) return base;
+  // (many haplotypes: the unit's tables once per unit, no hand-over records, no per-chain product tables)
+  if (call_use_wide(n_haps)) return ((base + 255) & ~(int64_t)255) + (int64_t)n_units * mchap_call_wide_unit_bytes(n_reads, n_haps, ploidy);
   return ((base + 255) & ~(int64_t)255) + call_state_bytes(n_units, n_haps, ploidy, chains) + call_ext_bytes(n_units, n_reads, n_haps, ploidy, chains);
 }
 // rounds of (settled chains a lane each, the chains that met a new context back on their wavefront) before the last launch runs
@@ -600,9 +619,51 @@ int mchap_call_mcmc_batch_device(int n_units, const double *reads, int n_reads, 
   if (steps < 1 || chains < 1 || chains > 65535) return fail(MCHAP_ERR_BAD_ARG, "steps and chains must be >= 1");
   if (ploidy < 1 || ploidy > MCHAP_MAX_PLOIDY_DENOVO) return fail(MCHAP_ERR_LIMIT, "ploidy %d not in 1..%d", ploidy, MCHAP_MAX_PLOIDY_DENOVO);
   if (n_reads < 1 || n_pos < 1 || max_allele < 1 || n_haps < 1) return fail(MCHAP_ERR_BAD_ARG, "empty shape");
-  if (n_haps > mchap::CALL_MAX_HAPS) return fail(MCHAP_ERR_LIMIT, "n_haps %d > %d", n_haps, mchap::CALL_MAX_HAPS);
+  if (n_haps > mchap_call_wide_max_haps())
+    return fail(MCHAP_ERR_LIMIT, "n_haps %d > %d (mchap_call_mcmc_max_haps: a chain's option arrays must fit the LDS)", n_haps, mchap_call_wide_max_haps());
   if (!cwr_fits(n_haps, ploidy)) return fail(MCHAP_ERR_LIMIT, "ploidy %d over %d haplotypes: more than 2^62 genotypes (the keys of the sampler's likelihood table are their ranks)", ploidy, n_haps);
   if (has_prior && !inbreeding) return fail(MCHAP_ERR_BAD_ARG, "prior requested without inbreeding");
+  if (call_use_wide(n_haps)) {
+    // (units are the grid's y: mchap_hip.h names the bound, application.call keeps its sub-batches within it)
+    if (n_units > 65535) return fail(MCHAP_ERR_LIMIT, "more than 65535 units in one call of the sampler over many haplotypes (n_haps %d > %d, or MCHAP_HIP_CALL_WIDE)", n_haps, mchap::CALL_MAX_HAPS);
+    const int64_t base = mchap_call_mcmc_workspace_bytes(n_units, n_haps, ploidy, steps, chains);
+    const int64_t need = mchap_call_mcmc_workspace_bytes_for(n_units, n_reads, n_haps, ploidy, steps, chains);
+    if (!workspace || workspace_bytes < need)
+      return fail(MCHAP_ERR_BAD_ARG, "workspace of %lld bytes is too small: %lld needed (mchap_call_mcmc_workspace_bytes_for)", (long long)workspace_bytes, (long long)need);
+    int rc = ensure_init();
+    if (rc) return rc;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    HIP_TRY(hipMemsetAsync(workspace, 0, (size_t)base, stream));
+    HIP_TRY(hipMemsetAsync(status, 0, sizeof(int32_t) * n_units, stream));
+    mchap::CallParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.reads = reads;
+    P.counts = read_counts;
+    P.haps = haplotypes;
+    P.inbreeding = has_prior ? inbreeding : nullptr;
+    P.freqs = has_prior ? frequencies : nullptr;
+    P.initial = initial;
+    P.stream_ids = stream_ids;
+    P.R = n_reads; P.M = n_pos; P.A = max_allele; P.H = n_haps; P.K = ploidy;
+    P.has_prior = has_prior;
+    P.step_type = step_type;
+    P.steps = steps;
+    P.chains = chains;
+    P.seed = seed;
+    P.cache = reinterpret_cast<ulonglong2 *>(workspace);
+    P.cache_slots = call_cache_slots(n_haps, ploidy, steps);
+    P.genotypes = genotypes;
+    P.llks = llks;
+    P.status = status;
+    P.n_units = n_units;
+    // (MCHAP_HIP_CALL_WIDE_CHAINS, tests: fewer chains of a unit per workgroup than the LDS holds -- the traces do not depend on it)
+    const char *e = std::getenv("MCHAP_HIP_CALL_WIDE_CHAINS");
+    const int wgc = mchap_call_wide_wg_chains(n_haps, chains, e ? std::atoi(e) : 0);
+    double *unit_tab = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(workspace) + ((base + 255) & ~(int64_t)255));
+    const int e2 = mchap_call_wide_launch(&P, unit_tab, wgc, stream);
+    if (e2) return fail(MCHAP_ERR_HIP, "call_wide_kernel: %s", hipGetErrorString((hipError_t)e2));
+    return MCHAP_OK;
+  }
   const int64_t ext = call_ext_bytes(n_units, n_reads, n_haps, ploidy, chains);
   // chains of a unit per workgroup (they share the unit's tables in LDS): as many as fit, one when the table is in the workspace
   int wgc = ext ? 1 : (chains < mchap::CALL_WG_CHAINS ? chains : mchap::CALL_WG_CHAINS);

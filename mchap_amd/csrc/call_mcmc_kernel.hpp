@@ -751,7 +751,7 @@ struct CallDraws {
 // banks).  A step is a serial program of ~1300 instructions whatever the number of lanes in use, so a batch is spread as thin as
 // the chip allows: few lanes per wavefront, a wavefront per SIMD (the host picks chains_per_wave).
 constexpr int CALL_COAST_WAVES = 4;
-__global__ __launch_bounds__(64 * CALL_COAST_WAVES) void call_coast_kernel(const CallParams P, const int chains_per_wave, const int lds_stride) {
+static __global__ __launch_bounds__(64 * CALL_COAST_WAVES) void call_coast_kernel(const CallParams P, const int chains_per_wave, const int lds_stride) {
   extern __shared__ __align__(16) unsigned char smem[];
   typedef __attribute__((address_space(3))) uint64_t lds_u64;
   typedef __attribute__((address_space(3))) const double lds_f64c;

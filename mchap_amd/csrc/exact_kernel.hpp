@@ -499,7 +499,7 @@ struct ExactModeParams {
   int64_t *mode_alleles;                  // [U][K] (output, and input of the second pass)
   double *mode_llk, *mode_prob, *total;   // [U]
 };
-__global__ __launch_bounds__(64) void exact_mode_kernel(const ExactModeParams P) {
+static __global__ __launch_bounds__(64) void exact_mode_kernel(const ExactModeParams P) {
   constexpr int KM = EXACT_KMAX;
   const ExactParams &E = P.e;
   const int unit = blockIdx.x;
@@ -653,7 +653,7 @@ struct ExactFreqParams {
   double *support_prob;     // [U] or null
   double *freqs_out, *occur_out;  // [U][H] or null
 };
-__global__ __launch_bounds__(64) void exact_freq_kernel(const ExactFreqParams P) {
+static __global__ __launch_bounds__(64) void exact_freq_kernel(const ExactFreqParams P) {
   const int unit = blockIdx.x;
   for (int h = threadIdx.x; h < 2 * P.H + 1; h += blockDim.x) {
     double sum = 0.0;

@@ -15,8 +15,8 @@ FILTERS = [
 # `assemble` only, not a reference filter: a target beyond the library's shape limits (README: SNVs per target, bits of sampled
 # alleles per haplotype) is written with null genotypes and this filter instead of being left out of the file
 LIMIT_FILTER = ("LIMIT", "Target not assembled: beyond the shape limits of this build (record kept with null genotypes)")
-# (the call programs: a record whose units the exact caller / call sampler does not take -- more than 2^62 genotypes, more than
-# 256 known haplotypes for the sampler, tables beyond the LDS -- is written with null genotypes and this filter, round 5)
+# (the call programs: a record whose units the exact caller / call sampler does not take -- more than 2^62 genotypes, more
+# known haplotypes than the sampler's bound (mchap_call_mcmc_max_haps of the library), tables beyond the LDS -- is written with null genotypes and this filter, round 5)
 LIMIT_FILTER_CALL = ("LIMIT", "Record not called: beyond the shape limits of this build (record kept with null genotypes)")
 
 # (id, Number, Type, Description); the order is the order of the header and of the INFO column

@@ -1,0 +1,107 @@
+"""CPU: `mchap call` over more than 256 known haplotypes -- the library's bound and workspace figures (no device needed: they are
+plain functions of the shape), and the program `application.call` with the sampler stubbed: a record of 300 alternate alleles is
+called like its neighbours and leaves their lines alone, a record beyond mchap_call_mcmc_max_haps is a FILTER=LIMIT record."""
+import io as _io
+import os
+
+import numpy as np
+import pytest
+
+from tests.call_wide_helpers import wide_vcf
+
+HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data")
+DEEP = ["simple.sample1.deep.bam", "simple.sample2.deep.bam", "simple.sample3.deep.bam"]
+
+
+def test_bound_and_workspace_figures(monkeypatch):
+    from mchap_amd import _lib
+
+    monkeypatch.delenv("MCHAP_HIP_CALL_WIDE", raising=False)
+    L = _lib.lib()
+    assert "mchap_call_mcmc_max_haps" in _lib.EXPORTS
+    for K in range(2, 9):
+        assert int(L.mchap_call_mcmc_max_haps(K)) >= 1024
+    assert int(L.mchap_call_mcmc_max_haps(0)) == 0 and int(L.mchap_call_mcmc_max_haps(99)) == 0
+    K, R, S, Cn = 4, 100, 2000, 2
+    for H in (300, 1024):
+        base = int(L.mchap_call_mcmc_workspace_bytes(1, H, K, S, Cn))
+        one = int(L.mchap_call_mcmc_workspace_bytes_for(1, R, H, K, S, Cn))
+        # the likelihood tables (2 x steps x K x H entries of 16 bytes a chain, a power of two) and the unit's product table, once
+        assert base >= Cn * 2 * S * K * H * 16
+        assert R * H * 8 <= one - base < 2 * R * H * 8 + (3 * K + 4) * H * 8 + 4096
+        # ... linear in the units: application.call sizes its sub-batches with the figure of one unit
+        assert int(L.mchap_call_mcmc_workspace_bytes_for(7, R, H, K, S, Cn)) == 7 * one
+    # up to 256 haplotypes the figure is what it was, and MCHAP_HIP_CALL_WIDE=1 sizes the other path's
+    narrow = int(L.mchap_call_mcmc_workspace_bytes_for(3, R, 16, K, S, Cn))
+    monkeypatch.setenv("MCHAP_HIP_CALL_WIDE", "1")
+    forced = int(L.mchap_call_mcmc_workspace_bytes_for(3, R, 16, K, S, Cn))
+    base = int(L.mchap_call_mcmc_workspace_bytes(3, 16, K, S, Cn))
+    assert narrow > base and forced >= base + 3 * R * 16 * 8 and forced != narrow
+
+
+def test_call_program_with_a_stubbed_sampler(tmp_path, monkeypatch, capsys):
+    from mchap_amd import _lib, application, cli
+    from mchap_amd.calling_mcmc import CallingMCMC, CallSummary
+
+    seen = []
+
+    def stub(self, reads, read_counts=None, initial=None, haplotypes=None, prior=None, stream_ids=None, burn=0, incongruence_threshold=0.6,
+             max_states=512, stream=None):
+        """a unit's genotype from its own reads alone: K copies of the haplotype that matches the reads' mean best"""
+        U, H, K = len(reads), haplotypes.shape[1], int(self.ploidy)
+        top = int(_lib.lib().mchap_call_mcmc_max_haps(K))
+        if H > top:  # (what mchap_call_mcmc_batch_device answers: MCHAP_ERR_LIMIT -> NotImplementedError)
+            raise NotImplementedError("mchap_hip: n_haps %d > %d (mchap_call_mcmc_max_haps)" % (H, top))
+        seen.append((U, H, K, reads.shape[1], reads.shape[2], reads.shape[3]))
+        done = []
+        n_obs = int(self.chains) * (int(self.steps) - burn)
+        for u in range(U):
+            mean = np.nan_to_num(np.nanmean(reads[u], axis=0))                       # [M, A]
+            score = mean[np.arange(haplotypes.shape[2])[None, :], haplotypes[u]].sum(axis=1)  # [H]
+            a = int(np.argmax(score))
+            done.append(CallSummary(genotypes=np.full((1, K), a, np.int32), counts=np.array([n_obs]), n_obs=n_obs, alleles=np.full(K, a, np.int32),
+                                    gprob=1.0, sprob=1.0, mci=0, n_allele=H))
+        return dict(done=done)
+
+    monkeypatch.setattr(CallingMCMC, "start_batch_summaries", stub)
+    monkeypatch.setattr(application, "_call_stream", lambda i: None)
+    budgets, budget = [], application.device_unit_budget
+
+    def recording_budget(bytes_per_unit, *a, **kw):
+        budgets.append(int(bytes_per_unit))
+        return budget(bytes_per_unit, *a, **kw)
+
+    monkeypatch.setattr(application, "device_unit_budget", recording_budget)
+    base = os.path.join(HERE, "simple.output.deep.assemble.vcf")
+    top = int(_lib.lib().mchap_call_mcmc_max_haps(4))
+    with_wide, with_both = str(tmp_path / "wide.vcf"), str(tmp_path / "both.vcf")
+    wide_vcf(base, with_wide, [("CHR1", 6, "WIDE300", 300)])
+    wide_vcf(base, with_both, [("CHR1", 6, "WIDE300", 300), ("CHR2", 11, "BEYOND", top + 1)])
+
+    def run(vcf):  # (application.call behind the command-line shell)
+        out = _io.StringIO()
+        cli.run(["mchap_amd", "call", "--bam"] + [os.path.join(HERE, f) for f in DEEP] + ["--ploidy", "4", "--haplotypes", vcf,
+                 "--mcmc-steps", "300", "--mcmc-burn", "100", "--mcmc-seed", "5", "--report", "AFP"], out)
+        return [ln for ln in out.getvalue().splitlines() if ln and not ln.startswith("#")]
+
+    plain, wide = run(base), run(with_wide)
+    capsys.readouterr()
+    assert len(wide) == len(plain) + 1
+    # the program sized the wide record's sub-batches with the figure that counts the unit's tables (_for), not the smaller one
+    (w_shape,) = {t for t in seen if t[1] == 301}
+    _, H, K, R, M, A = w_shape
+    L = _lib.lib()
+    ws1 = int(L.mchap_call_mcmc_workspace_bytes_for(1, R, H, K, 300, 2))
+    assert ws1 >= int(L.mchap_call_mcmc_workspace_bytes(1, H, K, 300, 2)) + R * H * 8
+    assert R * M * A * 8 + R * 8 + 2 * 300 * (K + 1) * 8 + ws1 + 4096 in budgets
+    rec = [ln.split("\t") for ln in wide]
+    assert all(f[6] != "LIMIT" for f in rec)
+    (w,) = [f for f in rec if f[2] == "WIDE300"]
+    assert len(w[4].split(",")) == 300 and all("." not in s.split(":")[0] for s in w[9:])
+    assert [ln for ln in wide if ln.split("\t")[2] != "WIDE300"] == plain
+    both = run(with_both)
+    err = capsys.readouterr().err
+    by = {ln.split("\t")[2]: ln.split("\t") for ln in both}
+    assert by["BEYOND"][6] == "LIMIT" and by["BEYOND"][9].split(":")[0] == "./././."
+    assert "not called" in err and "FILTER=LIMIT" in err and str(top) in err
+    assert [ln for ln in both if ln.split("\t")[2] != "BEYOND"] == wide
