@@ -398,6 +398,19 @@ int mchap_call_mcmc_batch(int n_units, const double *reads, int n_reads, int n_p
                           const double *frequencies, const int64_t *initial, const uint64_t *stream_ids, int steps, int chains,
                           int step_type, uint64_t seed, int64_t *genotypes, double *llks, int32_t *status);
 
+/* The read tensors of a shape group of `mchap call` / `mchap call-exact` from int8 allele calls (mchap_amd/blockpath.py
+ * call_unit_inputs builds the compact arrays): encoding.as_probabilistic / encode_read_distributions without base qualities, in
+ * the same order.  Cell (u, r, j, a) with r < unit_rows[u] is p_call if a == call, else p_other; NaN for every a if call < 0;
+ * 0.0 if a >= n_alleles[u][j] (applied last).  Rows r >= unit_rows[u] are NaN in every cell with count 0 (the programs' padding
+ * of a group to its deepest unit).  The host passes p_call = 1 - error_rate and p_other = (1 - p_call) / 3 in float64; the device
+ * does no arithmetic on them.  All pointers are device pointers (calls / counts may be NULL when no unit has a row); enqueues on
+ * `stream`, does not synchronise.  Environment (measurement and tests; the tensor does not depend on it):
+ * MCHAP_HIP_CALL_READS_WIDE=1 divides the cell index in 64 bits whatever the size (the default does below 2^32 cells in 32). */
+int mchap_call_reads_from_calls_device(int n_units, const int8_t *calls, const int64_t *counts, const int64_t *unit_rows,
+                                       const int64_t *unit_call_off, const int64_t *unit_count_off, const int8_t *n_alleles,
+                                       int n_reads, int n_pos, int max_allele, double p_call, double p_other, double *reads,
+                                       int64_t *read_counts, void *stream);
+
 /* Measurement (bench.py): a timer is a pair of HIP events owned by the caller.  A fit whose cfg.timer is set records them on
  * its own stream right around its sampler launches; mchap_timer_ms waits for the second event and returns the span in
  * milliseconds (< 0: nothing recorded).  No process-wide state: fits on different threads / streams use different timers. */

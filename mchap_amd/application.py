@@ -200,22 +200,98 @@ def _mec(calls, genotype):
     return int(diff.sum(axis=-1).min(axis=-1).sum())
 
 
-def _exact_units(records, source, samples, prior_tag, allele_filter=None):
+class _BlockReads:
+    """unit["reads"][sample] of a record on the block path: what ReadSource.reads returns (calls, depth, counts, the distinct
+    rows as `ucalls`) as views into the block's encoding; the float `dists` are formed from `ucalls` on first use -- --report GL,
+    the oracle replay -- and never for a unit whose tensor the device forms."""
+
+    __slots__ = ("d", "n_alleles", "error_rate")
+
+    def __init__(self, d, n_alleles, error_rate):
+        self.d, self.n_alleles, self.error_rate = d, n_alleles, error_rate
+
+    def __getitem__(self, key):
+        if key == "dists" and "dists" not in self.d:
+            self.d["dists"] = encoding.encode_read_distributions(self.n_alleles, self.d["ucalls"], None, error_rate=self.error_rate)
+        return self.d[key]
+
+
+def _block_encodings(loci, source, samples):
+    """blockpath.extract_block / encode_block over the loci of a block of records, once per sample (tables and look-up table
+    shared): dict(encs [per sample], si {sample: index}, nal int8 alleles of every SNV, error_rate)."""
+    from . import blockpath as bp
+
+    tables = bp.locus_tables(loci)
+    n_snv = int(tables[1][-1])
+    lut = bp.allele_lut(loci, n_snv)
+    encs = []
+    for sample in samples:
+        if isinstance(source, MatrixSource):
+            pile = bp.pile_from_matrices(loci, [source.codes(l.name, sample) for l in loci], tables=tables)
+        else:
+            name, path = source.pools[sample][0]
+            pile = bp.extract_block(loci, source.bams[path].columns(), name, tables=tables, **source.filter)
+        encs.append(bp.encode_block(loci, pile, lut))
+    nal = np.fromiter((a for l in loci for a in l.n_alleles), dtype=np.int8, count=n_snv)
+    return dict(encs=encs, si={s: i for i, s in enumerate(samples)}, nal=nal, error_rate=source.error_rate)
+
+
+def _exact_units(records, source, samples, prior_tag, allele_filter=None, block_path=False):
     """Everything `call-exact` needs from the input side, record by record: the locus, per sample the encoded reads,
     and which (record, sample) units need the kernel (a record with a single haplotype, or no variable position, has
-    one genotype with probability 1; an invalid record is not called at all)."""
+    one genotype with probability 1; an invalid record is not called at all).
+    block_path: False = the reads of every (record, sample) through source.reads (the definition); None / True = extracted and
+    encoded for the whole block at once (mchap_amd/blockpath.py; the caller has checked _block_path_takes(source)) -- a block
+    the array path does not take (BlockPathUnavailable) goes record by record."""
+    loci = [Locus(rec, prior_tag, allele_filter) for rec in records]
+    blk = None
+    if block_path is not False and loci:
+        from .blockpath import BlockPathUnavailable
+
+        try:
+            blk = _block_encodings(loci, source, samples)
+        except BlockPathUnavailable:
+            pass   # (an unsorted file, a row-hash collision: this block goes record by record, under True as well)
     out = []
-    for rec in records:
-        locus = Locus(rec, prior_tag, allele_filter)
+    for li, (rec, locus) in enumerate(zip(records, loci)):
         H, M = locus.haplotypes.shape
         invalid = None
         if locus.mask_reference_allele and H == 1:
             invalid = "NOA"
         elif np.any(np.isnan(locus.frequencies)):
             invalid = "AF0"
-        per = {s: source.reads(locus, s) for s in samples}
-        out.append(dict(rec=rec, locus=locus, invalid=invalid, reads=per, needs_kernel=(invalid is None and M > 0 and H > 1)))
+        if blk is None:
+            per = {s: source.reads(locus, s) for s in samples}
+        elif M == 0:
+            # (no variable position: nothing is sampled; the per-record encoder on the block's character matrix)
+            per = {s: encode_reads(locus, *blk["encs"][i].pile.matrices(li), source.error_rate, False) for s, i in blk["si"].items()}
+        else:
+            per = {s: _BlockReads(blk["encs"][i].per_locus(li), locus.n_alleles, source.error_rate) for s, i in blk["si"].items()}
+        out.append(dict(rec=rec, locus=locus, invalid=invalid, reads=per, needs_kernel=(invalid is None and M > 0 and H > 1),
+                        block=blk, li=li))
     return out
+
+
+def _group_compact_reads(units, members, Rmax, A):
+    """The reads of a chunk of a shape group as int8 calls of the units' distinct rows (device.CompactCallReads: its on_device()
+    is one call of mchap_call_reads_from_calls_device); None when the units do not come from a block encoding (the caller then
+    fills and uploads the float tensor)."""
+    blk = units[members[0][0]].get("block")
+    if blk is None or any(units[ri].get("block") is not blk for ri in {ri for ri, _ in members}):
+        return None
+    from . import blockpath as bp
+    from .device import CompactCallReads
+
+    li = np.fromiter((units[ri]["li"] for ri, _ in members), dtype=np.int64, count=len(members))
+    si = np.fromiter((blk["si"][s] for _, s in members), dtype=np.int64, count=len(members))
+    return CompactCallReads(*bp.call_unit_inputs(blk["encs"], li, si, blk["nal"]), Rmax, A, error_rate=blk["error_rate"])
+
+
+def _max_allele(sr, locus):
+    """A of a unit's read tensor."""
+    if isinstance(sr, _BlockReads):
+        return int(max(locus.n_alleles))
+    return sr["dists"].shape[2] if sr["dists"].ndim == 3 and sr["dists"].shape[0] else int(max(locus.n_alleles))
 
 
 def _run_exact_groups(units, ploidy_of, inbreeding_of, full, backend=None):
@@ -232,8 +308,7 @@ def _run_exact_groups(units, ploidy_of, inbreeding_of, full, backend=None):
         locus = unit["locus"]
         H, M = locus.haplotypes.shape
         for s, sr in unit["reads"].items():
-            A = sr["dists"].shape[2] if sr["dists"].ndim == 3 and sr["dists"].shape[0] else int(max(locus.n_alleles))
-            groups.setdefault((M, A, H, int(ploidy_of(s))), []).append((ri, s))
+            groups.setdefault((M, _max_allele(sr, locus), H, int(ploidy_of(s))), []).append((ri, s))
     results = {}
     for (M, A, H, K), members in groups.items():
         if backend is not None:
@@ -244,7 +319,7 @@ def _run_exact_groups(units, ploidy_of, inbreeding_of, full, backend=None):
                 prior = None if F is None else (F, locus.frequencies)
                 results[(ri, s)] = _exact_one(backend, sr, locus.haplotypes, K, prior, full)
             continue
-        Rmax = max(max(len(units[ri]["reads"][s]["dists"]), 1) for ri, s in members)
+        Rmax = max(max(len(units[ri]["reads"][s]["counts"]), 1) for ri, s in members)  # (distinct rows: as many as counts)
         from math import comb
 
         G = comb(H + K - 1, K)
@@ -269,24 +344,32 @@ def _run_exact_groups(units, ploidy_of, inbreeding_of, full, backend=None):
                         units[ri]["invalid"] = sub_units[i]["invalid"]
             continue
         U = len(members)
-        reads = np.full((U, Rmax, M, A), np.nan)
-        counts = np.zeros((U, Rmax), dtype=np.int64)
+        # a group of the block path: int8 calls up, the float tensor formed on the device; else filled here and uploaded
+        compact = _group_compact_reads(units, members, Rmax, A)
+        if compact is None:
+            reads = np.full((U, Rmax, M, A), np.nan)
+            counts = np.zeros((U, Rmax), dtype=np.int64)
         haps = np.zeros((U, H, M), dtype=np.int8)
         Fs = np.zeros(U)
         frs = np.zeros((U, H))
         has_prior = inbreeding_of(members[0][1]) is not None
         for i, (ri, s) in enumerate(members):
             sr, locus = units[ri]["reads"][s], units[ri]["locus"]
-            n = len(sr["dists"])
-            if n:
-                reads[i, :n] = sr["dists"]
-                counts[i, :n] = sr["counts"]
+            if compact is None:
+                n = len(sr["dists"])
+                if n:
+                    reads[i, :n] = sr["dists"]
+                    counts[i, :n] = sr["counts"]
             haps[i] = locus.haplotypes
             if has_prior:
                 Fs[i] = inbreeding_of(s)
                 frs[i] = locus.frequencies
         try:
-            batch = ExactDeviceBatch(reads, K, haps, counts, (Fs, frs) if has_prior else None)
+            if compact is None:
+                batch = ExactDeviceBatch(reads, K, haps, counts, (Fs, frs) if has_prior else None)
+            else:
+                on_device = compact.on_device()
+                batch = ExactDeviceBatch.from_device_reads(on_device[0], K, haps, on_device[1], (Fs, frs) if has_prior else None)
             batch.run(streaming=not full, arrays=full)
         except NotImplementedError as e:
             # a shape the library does not take (more than 2^62 genotypes, ploidy above 15, tables beyond the LDS): the records
@@ -486,17 +569,25 @@ def _blocks(items, n):
 
 def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.0024, use_base_phred_scores=False,
                prior_frequencies_tag=None, inbreeding=None, calling=None, filter_input_haplotypes=None, read_kw=None,
-               records_per_block=4096, shard=None):
+               records_per_block=4096, shard=None, block_path=None):
     """`mchap call-exact` over a VCF of known haplotypes: yields one VCF record line per input record (no header).
     sample_bams: ordered mapping sample name -> BAM path (or pool -> [(sample, path)], or a ReadSource); ploidy /
     inbreeding: a value or {sample: value}.  The records are processed in blocks: the (record x sample) units of a block
     are encoded, grouped by shape and evaluated in one device call per shape (cut further when a group would not fit the
     free HBM), and the block's lines are yielded before the next block is read: host and device memory stay bounded by
     the block, as with the reference's record-by-record stream.  shard = (rank, world): this process's contiguous share
-    of the records (mchap_amd.shard.shard_range)."""
+    of the records (mchap_amd.shard.shard_range).
+
+    block_path: True = the reads of a block of records are extracted and encoded as array operations over the whole block
+    (mchap_amd/blockpath.py), int8 calls are uploaded and the read tensors formed on the device; the source must allow it --
+    alignment files read whole, one file per sample, base qualities ignored -- or the call fails (a single block the array
+    path refuses -- an unsorted file, a row-hash collision -- goes record by record instead); False = always record by
+    record (the definition: tests hold the two against each other line for line); None = the block path where the inputs allow
+    it and CALL_BLOCK_PATH_DEFAULT is set, else record by record.  A `calling` backend is evaluated unit by unit either way."""
     from .vcfheader import report_fields
 
     source = _source(sample_bams, base_error_rate, use_base_phred_scores, read_kw)
+    block_path = _call_block_path(block_path, source)
     samples = source.samples
     _, records = read_vcf(vcf_path)
     records = _shard(records, shard)
@@ -505,7 +596,7 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
     ploidy_of, inbreeding_of = _per_sample(ploidy, samples), _per_sample(inbreeding, samples)
     allele_filter = _allele_filter(vcf_path, filter_input_haplotypes)
     for block in _blocks(records, records_per_block):
-        units = _exact_units(block, source, samples, prior_frequencies_tag, allele_filter)
+        units = _exact_units(block, source, samples, prior_frequencies_tag, allele_filter, block_path)
         results = _run_exact_groups(units, ploidy_of, inbreeding_of, full, calling)
         for ri, unit in enumerate(units):
             rec = unit["rec"]
@@ -1008,6 +1099,23 @@ def _block_path_takes(source):
     return True
 
 
+# What block_path=None means to call / call_exact where the source takes the block path.  False: the block path is shipped behind
+# the keyword (block_path=True) until tools/call_e2e_once.py has shown it faster than the per-record path for both programs on an
+# MI355X (not measured yet); the programs then use it by default.
+CALL_BLOCK_PATH_DEFAULT = False
+
+
+def _call_block_path(block_path, source):
+    """The block_path keyword of call / call_exact as _exact_units takes it: False when the source needs the per-record path."""
+    if block_path is False or (block_path is None and not CALL_BLOCK_PATH_DEFAULT):
+        return False
+    if not _block_path_takes(source):
+        if block_path is True:
+            raise ValueError("block_path=True: the inputs need the per-record path")
+        return False
+    return block_path
+
+
 def _rounded_text(r):
     """io._number_text of a value already rounded by np.round (an array's worth at a time)."""
     if r != r:
@@ -1421,15 +1529,16 @@ class _BlockState:
 def call(vcf_path, sample_bams, ploidy=2, report=(), base_error_rate=0.0024, use_base_phred_scores=False,
          prior_frequencies_tag=None, inbreeding=None, steps=2000, burn=1000, chains=2, seed=42,
          incongruence_threshold=0.60, step_type="Gibbs", filter_input_haplotypes=None, read_kw=None, records_per_block=1024,
-         shard=None):
+         shard=None, block_path=None):
     """`mchap call`: yields one VCF record line per record of the input VCF (no header).  The records are processed in
     blocks; the (record x sample) units of a block are grouped by shape and each group is one launch of the sampler kernel
     (CallingMCMC.fit_batch), cut into several when its traces and per-chain likelihood tables would not fit the free HBM.
-    As in the reference every unit restarts from the same seed."""
+    As in the reference every unit restarts from the same seed.  block_path: as call_exact's."""
     from .calling_mcmc import CallingMCMC, CallSummary, GenotypeAllelesMultiTrace
     from . import _lib, calling
 
     source = _source(sample_bams, base_error_rate, use_base_phred_scores, read_kw)
+    block_path = _call_block_path(block_path, source)
     samples = source.samples
     seed = resolve_seed(seed)
     _, records = read_vcf(vcf_path)
@@ -1438,7 +1547,7 @@ def call(vcf_path, sample_bams, ploidy=2, report=(), base_error_rate=0.0024, use
     ploidy_of, inbreeding_of = _per_sample(ploidy, samples), _per_sample(inbreeding, samples)
     allele_filter = _allele_filter(vcf_path, filter_input_haplotypes)
     for block in _blocks(records, records_per_block):
-        units = _exact_units(block, source, samples, prior_frequencies_tag, allele_filter)
+        units = _exact_units(block, source, samples, prior_frequencies_tag, allele_filter, block_path)
         # haplotypes with zero prior frequency (and a masked reference) are left out of the sampler (call.py:72-84)
         groups = {}
         for ri, unit in enumerate(units):
@@ -1458,24 +1567,31 @@ def call(vcf_path, sample_bams, ploidy=2, report=(), base_error_rate=0.0024, use
         results = {}
         pending = []
         for (M, A, H, K), all_members in groups.items():
-            Rmax = max(max(len(units[ri]["reads"][s]["dists"]), 1) for ri, s in all_members)
+            Rmax = max(max(len(units[ri]["reads"][s]["counts"]), 1) for ri, s in all_members)  # (distinct rows: as many as counts)
             # device bytes per unit: reads, traces, and the chains' tables of remembered likelihoods (the workspace)
             ws1 = int(_lib.lib().mchap_call_mcmc_workspace_bytes_for(1, Rmax, H, K, int(steps), int(chains)))
             per_unit = Rmax * M * A * 8 + Rmax * 8 + chains * steps * (K + 1) * 8 + ws1 + 4096
             # (at most 65535 units a call: the bound of the sampler over more than 256 haplotypes, include/mchap_hip.h)
             for members in _blocks(all_members, min(65535, device_unit_budget(per_unit))):
                 U = len(members)
-                reads = np.full((U, Rmax, M, A), np.nan)
-                counts = np.zeros((U, Rmax), dtype=np.int64)
+                # a group of the block path: int8 calls up, the float tensor formed on the device (on the batch's stream); else
+                # filled here and uploaded
+                compact = _group_compact_reads(units, members, Rmax, A)
+                if compact is not None:
+                    reads, counts = compact, compact.counts
+                else:
+                    reads = np.full((U, Rmax, M, A), np.nan)
+                    counts = np.zeros((U, Rmax), dtype=np.int64)
                 haps = np.zeros((U, H, M), dtype=np.int8)
                 has_prior = inbreeding_of(members[0][1]) is not None
                 Fs, frs = np.zeros(U), np.zeros((U, H))
                 for i, (ri, s) in enumerate(members):
                     sr, locus = units[ri]["reads"][s], units[ri]["locus"]
-                    n = len(sr["dists"])
-                    if n:
-                        reads[i, :n] = sr["dists"]
-                        counts[i, :n] = sr["counts"]
+                    if compact is None:
+                        n = len(sr["dists"])
+                        if n:
+                            reads[i, :n] = sr["dists"]
+                            counts[i, :n] = sr["counts"]
                     haps[i] = locus.haplotypes[units[ri]["keep"]]
                     if has_prior:
                         Fs[i] = inbreeding_of(s)
@@ -1517,7 +1633,14 @@ def call(vcf_path, sample_bams, ploidy=2, report=(), base_error_rate=0.0024, use
                         r["GP"] = summ.posterior().as_array(H)
                     if "GL" in report or "FORMAT/GL" in report:
                         sr = unit["reads"][s]
-                        r["GL"] = calling.genotype_likelihoods(sr["dists"], K, locus.haplotypes, read_counts=sr["counts"]).astype(np.float64) / np.log(10)
+                        if M == 0:
+                            # no variable position: every read has likelihood 1 under the one genotype there is (the exact caller
+                            # takes no tensor without positions; call-exact writes the same zero)
+                            from math import comb
+
+                            r["GL"] = np.zeros(comb(H + K - 1, K))
+                        else:
+                            r["GL"] = calling.genotype_likelihoods(sr["dists"], K, locus.haplotypes, read_counts=sr["counts"]).astype(np.float64) / np.log(10)
                     res[(ri, s)] = r
             flt, info, fmt, cols = _format_exact_record(dict(unit, invalid=unit["invalid"]), samples, _Forced(res), ri, ploidy_of, report, prior_frequencies_tag)
             # MCI is a sampler statistic here: per sample in the FORMAT column, the number of incongruent samples in INFO

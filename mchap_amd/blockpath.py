@@ -289,6 +289,68 @@ def unit_inputs(enc, use):
     return calls, counts, R, off, np.where(nu > 0, c_off, -1)
 
 
+def call_unit_inputs(encs, loci, samples, n_alleles):
+    """The compact input of a shape group of `mchap call` / `mchap call-exact` (mchap_call_reads_from_calls_device): the group's
+    units are the (locus loci[i], sample samples[i]) pairs -- indices into the block's loci and into `encs`, the samples'
+    encodings --, all with the same number M >= 1 of SNVs.  n_alleles: int8, the alleles at every SNV of the block's loci,
+    concatenated (the order of locus_tables' positions).  Returns (int8 calls of the units' distinct rows, unit after unit, their
+    counts, rows per unit [U], first call element [U], first count [U], n_alleles int8 [U, M]).  A unit without reads has 0 rows
+    (not unit_inputs' all-gap row: the call programs pad a group with rows of weight 0)."""
+    loci, samples = np.asarray(loci, dtype=np.int64), np.asarray(samples, dtype=np.int64)
+    U = len(loci)
+    pile = encs[0].pile
+    Ms = pile.M[loci]
+    M = int(Ms[0]) if U else 0
+    if U and (M < 1 or (Ms != M).any()):
+        raise ValueError("call_unit_inputs: the units of a group share one number (>= 1) of SNVs")
+    nu = np.zeros(U, dtype=np.int64)
+    src_cell = np.zeros(U, dtype=np.int64)
+    src_row = np.zeros(U, dtype=np.int64)
+    members = [(int(s), np.flatnonzero(samples == s)) for s in np.unique(samples)]  # (a loop over samples, never over units)
+    for s, idx in members:
+        e = encs[s]
+        nu[idx] = (e.urow_start[1:] - e.urow_start[:-1])[loci[idx]]
+        src_cell[idx] = e.ucell_start[loci[idx]]
+        src_row[idx] = e.urow_start[loci[idx]]
+    cells = nu * M
+    call_off = np.cumsum(cells) - cells
+    count_off = np.cumsum(nu) - nu
+    calls = np.empty(int(cells.sum()), dtype=np.int8)
+    counts = np.empty(int(nu.sum()), dtype=np.int64)
+    for s, idx in members:
+        e = encs[s]
+        owner, k = _ragged_arange(cells[idx])
+        calls[call_off[idx][owner] + k] = e.ucalls[src_cell[idx][owner] + k]
+        owner, k = _ragged_arange(nu[idx])
+        counts[count_off[idx][owner] + k] = e.ucounts[src_row[idx][owner] + k]
+    nal = np.asarray(n_alleles, dtype=np.int8)[pile.snv_start[loci][:, None] + np.arange(M, dtype=np.int64)[None, :]]
+    return calls, counts, nu, call_off, count_off, nal.reshape(U, M)
+
+
+def expand_call_units(calls, counts, unit_rows, unit_call_off, unit_count_off, n_alleles, n_reads, max_allele, error_rate=0.0024):
+    """What mchap_call_reads_from_calls_device writes, on the host (the rule of include/mchap_hip.h; the tests hold the kernel and
+    the programs' fill loop against it): (reads float64 [U, n_reads, M, max_allele], read_counts int64 [U, n_reads])."""
+    nal = np.asarray(n_alleles, dtype=np.int64)
+    U, M = nal.shape
+    R, A = int(n_reads), int(max_allele)
+    rows = np.asarray(unit_rows, dtype=np.int64)
+    p_call = 1.0 - error_rate
+    p_other = (1.0 - p_call) / 3.0
+    padded = np.full((U, R, M), -1, dtype=np.int64)
+    read_counts = np.zeros((U, R), dtype=np.int64)
+    u, r = _ragged_arange(rows)
+    if len(u):
+        src = np.asarray(unit_call_off, dtype=np.int64)[u] + r * M
+        padded[u, r] = np.asarray(calls)[src[:, None] + np.arange(M, dtype=np.int64)[None, :]]
+        read_counts[u, r] = np.asarray(counts)[np.asarray(unit_count_off, dtype=np.int64)[u] + r]
+    allele = np.arange(A, dtype=np.int64)
+    reads = np.where(padded[..., None] == allele, p_call, p_other)
+    reads = np.where((padded < 0)[..., None], np.nan, reads)
+    reads = np.where(allele >= nal[:, None, :, None], 0.0, reads)
+    reads[np.arange(R)[None, :] >= rows[:, None]] = np.nan   # (padding rows: NaN in every cell)
+    return reads, read_counts
+
+
 def unpack_words(words, unit, fixed, fixed_off, M, bits):
     """Packed haplotype words -> allele rows, for words of many units at once: words uint64 [n], unit [n] (index of each
     word's unit), fixed int8 (the batch's fixed-allele templates, unit u at fixed_off[u] .. + M[u]), bits [U] bits per sampled

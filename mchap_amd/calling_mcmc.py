@@ -121,14 +121,32 @@ class CallingMCMC(Assembler):
                                                                       incongruence_threshold, max_states))
 
     def start_batch_summaries(self, reads, read_counts=None, initial=None, haplotypes=None, prior=None, stream_ids=None, burn=0,
-                              incongruence_threshold=0.6, max_states=512, stream=None):
+                              incongruence_threshold=0.6, max_states=512, stream=None, device_reads=None):
         """The first half of fit_batch_summaries: uploads, the sampler and the summary launches enqueued on `stream` (a
         torch.cuda.Stream; default: the current one) without waiting for them -- several batches (the shapes of a block of
-        records) then run side by side.  Returns the handle finish_batch_summaries takes."""
-        from .device import _torch
+        records) then run side by side.  Returns the handle finish_batch_summaries takes.
 
-        reads = np.ascontiguousarray(reads, dtype=np.float64)
-        U, R, M, A = reads.shape
+        device_reads: (reads float64 torch tensor [U, R, M, A] with M, R >= 1, read_counts int64 torch tensor [U, R] or None) that
+        are on the device already (device.call_reads_from_calls, enqueued on `stream`): they take the place of `reads` and
+        `read_counts`, which are then not looked at.  `reads` may also be a device.CompactCallReads (int8 calls of the units'
+        distinct rows: the block path of `mchap call`): its tensors are formed on the device, on `stream`."""
+        from .device import CompactCallReads, _torch
+
+        if device_reads is None and isinstance(reads, CompactCallReads):
+            torch = _torch()
+            with (torch.cuda.stream(stream) if stream is not None else _null_context()):
+                device_reads = reads.on_device()
+        if device_reads is not None:
+            t_reads, t_counts = device_reads
+            U, R, M, A = (int(x) for x in t_reads.shape)
+            assert M >= 1 and R >= 1 and t_reads.is_contiguous() and (t_counts is None or tuple(t_counts.shape) == (U, R))
+            if int(self.ploidy) > _lib.MAX_PLOIDY:  # (the host classes on downloaded traces, below: from host arrays)
+                reads = t_reads.cpu().numpy()
+                read_counts = None if t_counts is None else t_counts.cpu().numpy()
+                device_reads = None
+        if device_reads is None:
+            reads = np.ascontiguousarray(reads, dtype=np.float64)
+            U, R, M, A = reads.shape
         haps = np.asarray(self.haplotypes if haplotypes is None else haplotypes, dtype=np.int8)
         if haps.ndim == 2:
             haps = np.broadcast_to(haps, (U,) + haps.shape)
@@ -160,7 +178,10 @@ class CallingMCMC(Assembler):
                     fr = np.array(np.broadcast_to(np.asarray(pr[1], dtype=np.float64), (U, H)))
             up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
             p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-            d_reads, d_rc, d_haps = up(reads, np.float64), up(read_counts, np.int64), up(haps, np.int8)
+            if device_reads is not None:
+                d_reads, d_rc, d_haps = t_reads, t_counts, up(haps, np.int8)
+            else:
+                d_reads, d_rc, d_haps = up(reads, np.float64), up(read_counts, np.int64), up(haps, np.int8)
             d_F, d_fr, d_ini = up(F, np.float64), up(fr, np.float64), up(initial, np.int64)
             if initial is not None:
                 assert tuple(d_ini.shape) == (U, K)

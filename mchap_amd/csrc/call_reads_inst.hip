@@ -1,0 +1,67 @@
+// C ABI of the read-tensor fill of `mchap call` / `mchap call-exact` (call_reads_kernel.hpp; declared in include/mchap_hip.h).
+// Device pointers, a hipStream_t passed as void*, enqueue and return: the caller (mchap_amd/device.py) owns every buffer.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstdlib>
+
+#include "../../include/mchap_hip.h"
+#include "call_reads_kernel.hpp"
+
+namespace mchap {
+int set_last_error(int code, const char *msg);
+}
+
+namespace {
+
+unsigned grid_of(int64_t n) {
+  const int64_t nb = (n + mchap::CALL_READS_THREADS - 1) / mchap::CALL_READS_THREADS;
+  return (unsigned)(nb < mchap::CALL_READS_MAX_BLOCKS ? nb : mchap::CALL_READS_MAX_BLOCKS);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mchap_call_reads_from_calls_device(int n_units, const int8_t *calls, const int64_t *counts, const int64_t *unit_rows,
+                                       const int64_t *unit_call_off, const int64_t *unit_count_off, const int8_t *n_alleles,
+                                       int n_reads, int n_pos, int max_allele, double p_call, double p_other, double *reads,
+                                       int64_t *read_counts, void *stream) {
+  if (n_units <= 0) return MCHAP_OK;
+  if (n_reads < 1 || n_pos < 1 || max_allele < 1)
+    return mchap::set_last_error(MCHAP_ERR_BAD_ARG, "call reads: n_reads, n_pos and max_allele must be at least 1");
+  // (calls / counts may be NULL when no unit has a row: they are then never read)
+  if (!unit_rows || !unit_call_off || !unit_count_off || !n_alleles || !reads || !read_counts)
+    return mchap::set_last_error(MCHAP_ERR_BAD_ARG, "call reads: NULL buffer");
+  mchap::CallReadsParams P;
+  P.calls = calls;
+  P.counts = counts;
+  P.unit_rows = unit_rows;
+  P.unit_call_off = unit_call_off;
+  P.unit_count_off = unit_count_off;
+  P.n_alleles = n_alleles;
+  P.n_units = n_units;
+  P.R = n_reads;
+  P.M = n_pos;
+  P.A = max_allele;
+  P.p_call = p_call;
+  P.p_other = p_other;
+  P.reads = reads;
+  P.read_counts = read_counts;
+  const int64_t rows = (int64_t)n_units * n_reads;
+  const int64_t cells = rows * ((int64_t)n_pos * max_allele);
+  // (MCHAP_HIP_CALL_READS_WIDE=1 -- measurement and tests; the tensor does not depend on it -- divides in 64 bits whatever the size)
+  const char *wide = getenv("MCHAP_HIP_CALL_READS_WIDE");
+  if (cells < ((int64_t)1 << 32) && !(wide && wide[0] == '1'))
+    hipLaunchKernelGGL(mchap::call_reads_kernel<uint32_t>, dim3(grid_of(cells)), dim3(mchap::CALL_READS_THREADS), 0, (hipStream_t)stream, P);
+  else
+    hipLaunchKernelGGL(mchap::call_reads_kernel<int64_t>, dim3(grid_of(cells)), dim3(mchap::CALL_READS_THREADS), 0, (hipStream_t)stream, P);
+  hipLaunchKernelGGL(mchap::call_read_counts_kernel, dim3(grid_of(rows)), dim3(mchap::CALL_READS_THREADS), 0, (hipStream_t)stream, P);
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return MCHAP_OK;
+  char buf[256];
+  snprintf(buf, sizeof(buf), "call_reads_kernel: %s", hipGetErrorString(e));
+  return mchap::set_last_error(MCHAP_ERR_HIP, buf);
+}
+
+}  // extern "C"

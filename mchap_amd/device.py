@@ -266,6 +266,102 @@ class DenovoDeviceBatch(_OwnBuffers):
         )
 
 
+def call_reads_from_calls(calls, counts, unit_rows, unit_call_off, unit_count_off, n_alleles, n_reads, max_allele, error_rate=0.0024,
+                          device=None):
+    """The read tensors of a shape group of `mchap call` / `mchap call-exact`, formed on the device from the compact arrays of
+    blockpath.call_unit_inputs (mchap_call_reads_from_calls_device): int8 calls of the units' distinct rows, their counts, rows per
+    unit [U], the two offset arrays [U], n_alleles int8 [U, M].  Uploads them and enqueues the fill on torch's current stream (no
+    synchronisation).  Returns (reads float64 [U, n_reads, M, max_allele], read_counts int64 [U, n_reads]) as torch tensors:
+    encoding.encode_read_distributions of every unit's rows without qualities, padded to n_reads with NaN rows of count 0."""
+    torch = _torch()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    calls = np.ascontiguousarray(calls, dtype=np.int8).reshape(-1)
+    counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    rows = np.ascontiguousarray(unit_rows, dtype=np.int64)
+    c_off = np.ascontiguousarray(unit_call_off, dtype=np.int64)
+    n_off = np.ascontiguousarray(unit_count_off, dtype=np.int64)
+    nal = np.ascontiguousarray(n_alleles, dtype=np.int8)
+    U, M = nal.shape
+    R, A = int(n_reads), int(max_allele)
+    if not (rows.shape == c_off.shape == n_off.shape == (U,)) or R < 1 or M < 1 or A < 1:
+        raise AssertionError("call_reads_from_calls: per-unit arrays of one length, n_reads, positions and max_allele at least 1")
+    # (the kernel reads calls / counts at these offsets: checked here, where the arrays are still on the host)
+    if U and (rows.min() < 0 or rows.max() > R or c_off.min() < 0 or n_off.min() < 0 or (c_off + rows * M).max() > len(calls)
+              or (n_off + rows).max() > len(counts)):
+        raise AssertionError("call_reads_from_calls: a unit's rows lie outside calls / counts, or exceed n_reads")
+    up = lambda a: torch.from_numpy(a).to(dev) if a.size else None  # noqa: E731
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    d_in = [up(a) for a in (calls, counts, rows, c_off, n_off, nal.reshape(-1))]
+    d_reads = torch.empty((U, R, M, A), dtype=torch.float64, device=dev)
+    d_counts = torch.empty((U, R), dtype=torch.int64, device=dev)
+    p_call = 1.0 - error_rate             # (as encoding.encode_read_distributions / as_probabilistic form them)
+    p_other = (1.0 - p_call) / 3.0
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().mchap_call_reads_from_calls_device(
+            U, *[p(t) for t in d_in], R, M, A, C.c_double(p_call), C.c_double(p_other), p(d_reads), p(d_counts), C.c_void_p(stream)))
+    # (the inputs were allocated and are consumed on this stream: the allocator reuses them only for later work of the same stream)
+    return d_reads, d_counts
+
+
+class CompactCallReads:
+    """The reads of a shape group of `mchap call` / `mchap call-exact` in the compact form of blockpath.call_unit_inputs, standing
+    where the float64 [U, n_reads, M, max_allele] tensor does: `shape`, `len`, indexing and numpy conversion give that tensor
+    (formed on the host by blockpath.expand_call_units when someone asks for it: a stand-in sampler of the tests, the host classes
+    on downloaded traces), `counts` the [U, n_reads] counts in the same way, and on_device() both as device tensors formed there
+    from the int8 calls -- what CallingMCMC.start_batch_summaries and application._run_exact_groups use."""
+
+    ndim, dtype = 4, np.dtype(np.float64)
+
+    def __init__(self, calls, counts, unit_rows, unit_call_off, unit_count_off, n_alleles, n_reads, max_allele, error_rate=0.0024):
+        self.compact = (calls, counts, unit_rows, unit_call_off, unit_count_off, n_alleles)
+        self.n_reads, self.max_allele, self.error_rate = int(n_reads), int(max_allele), error_rate
+        self.shape = (n_alleles.shape[0], self.n_reads, n_alleles.shape[1], self.max_allele)
+        self.counts = _CompactCallCounts(self)
+        self._host = None
+
+    def on_device(self, device=None):
+        """(reads, read_counts) device tensors, the fill enqueued on torch's current stream."""
+        return call_reads_from_calls(*self.compact, self.n_reads, self.max_allele, error_rate=self.error_rate, device=device)
+
+    def on_host(self):
+        if self._host is None:
+            from .blockpath import expand_call_units
+
+            self._host = expand_call_units(*self.compact, self.n_reads, self.max_allele, error_rate=self.error_rate)
+        return self._host
+
+    def __len__(self):
+        return self.shape[0]
+
+    def __getitem__(self, i):
+        return self.on_host()[0][i]
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.on_host()[0]
+        return a if dtype is None else a.astype(dtype, copy=False)
+
+
+class _CompactCallCounts:
+    """CompactCallReads.counts: the [U, n_reads] int64 counts, formed with the tensor."""
+
+    ndim, dtype = 2, np.dtype(np.int64)
+
+    def __init__(self, reads):
+        self.reads = reads
+        self.shape = reads.shape[:2]
+
+    def __len__(self):
+        return self.shape[0]
+
+    def __getitem__(self, i):
+        return self.reads.on_host()[1][i]
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.reads.on_host()[1]
+        return a if dtype is None else a.astype(dtype, copy=False)
+
+
 class ExactDeviceBatch:
     """A batch of exact-caller units that share a shape, resident on one GPU: inputs are uploaded once, every output of
     mchap_exact_call_batch_device stays in HBM until asked for.
@@ -275,11 +371,33 @@ class ExactDeviceBatch:
 
     def __init__(self, reads, ploidy, haplotypes, read_counts=None, prior=None, device=None, cache_joint=True):
         torch = _torch()
-        self.torch = torch
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        dev = self.device
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         reads = np.ascontiguousarray(reads, dtype=np.float64)
-        U, R, M, A = reads.shape
+        d_reads = torch.from_numpy(reads.reshape(-1)).to(dev)
+        d_counts = None if read_counts is None else torch.from_numpy(
+            np.ascontiguousarray(read_counts, dtype=np.int64).reshape(-1)).to(dev)
+        self._setup(d_reads, reads.shape, ploidy, haplotypes, d_counts, prior, dev, cache_joint)
+
+    @classmethod
+    def from_device_reads(cls, reads, ploidy, haplotypes, read_counts=None, prior=None, device=None, cache_joint=True):
+        """The batch over read tensors that are on the device already (call_reads_from_calls): reads a float64 torch tensor
+        [U, R, M, A], read_counts an int64 torch tensor [U, R] or None; the other arguments as the constructor's.  Nothing is
+        copied: the batch keeps the tensors."""
+        torch = _torch()
+        assert reads.dtype == torch.float64 and reads.dim() == 4 and reads.is_contiguous()
+        if read_counts is not None:
+            assert read_counts.dtype == torch.int64 and tuple(read_counts.shape) == tuple(reads.shape[:2]) and read_counts.is_contiguous()
+        self = cls.__new__(cls)
+        self._setup(reads.reshape(-1), tuple(reads.shape), ploidy, haplotypes, None if read_counts is None else read_counts.reshape(-1),
+                    prior, reads.device if device is None else device, cache_joint)
+        return self
+
+    def _setup(self, d_reads, shape, ploidy, haplotypes, d_counts, prior, dev, cache_joint):
+        """Everything after the reads are on the device: haplotypes, prior, workspace."""
+        torch = _torch()
+        self.torch = torch
+        self.device = dev
+        U, R, M, A = (int(x) for x in shape)
         haps = np.asarray(haplotypes, dtype=np.int8)
         if haps.ndim == 2:
             haps = np.broadcast_to(haps, (U,) + haps.shape)
@@ -289,10 +407,9 @@ class ExactDeviceBatch:
         from math import comb
 
         self.G = comb(H + int(ploidy) - 1, int(ploidy))
-        self.d_reads = torch.from_numpy(reads.reshape(-1)).to(dev)
+        self.d_reads = d_reads
         self.d_haps = torch.from_numpy(haps.reshape(-1)).to(dev)
-        self.d_counts = None if read_counts is None else torch.from_numpy(
-            np.ascontiguousarray(read_counts, dtype=np.int64).reshape(-1)).to(dev)
+        self.d_counts = d_counts
         self.has_prior = 0 if prior is None else 1
         self.d_F = self.d_fr = None
         if prior is not None:
