@@ -155,8 +155,27 @@ __device__ inline double calling_log_prior_unsorted(const PriorTab &t, const int
   return t.left + prod;
 }
 
-__device__ __forceinline__ long long call_key(const int *g, int K) {
-  int s[EXACT_KMAX];
+// C(n + k - 1, k) without an intermediate beyond the result: cwr of exact_kernel.hpp forms r * (n - 1 + d) before it divides, up to
+// k times the count -- past 2^63 where the count itself stays below the 2^62 the shape rule admits (ploidy 11 over 206 haplotypes,
+// ploidy 15 over 93; a thousand haplotypes at ploidy 7).  Here r = q d + rem gives r m / d = q m + rem m / d, the first term a
+// multiple of m below the result and rem m < d m.  The same values wherever cwr is right.
+__device__ __forceinline__ long long call_cwr(int n, int k) {
+  if (n <= 0) return 0;
+  long long r = 1;
+  for (int d = 1; d <= k; d++) {
+    const long long m = n - 1 + d;
+    r = (r / d) * m + ((r % d) * m) / d;
+  }
+  return r;
+}
+// The rank of the sampler's keys: ascending alleles -> VCF index (jitutils.py:253-276), right for every shape below 2^62 genotypes
+__device__ __forceinline__ long long call_rank(const int *sorted, int K) {
+  long long idx = 0;
+  for (int i = 0; i < K; i++) idx += call_cwr(sorted[i], i + 1);
+  return idx;
+}
+template <int KM>
+__device__ __forceinline__ void call_sorted(const int *g, int K, int (&s)[KM]) {
   for (int i = 0; i < K; i++) s[i] = g[i];
   for (int a = 1; a < K; a++) {  // insertion sort
     const int v = s[a];
@@ -167,7 +186,24 @@ __device__ __forceinline__ long long call_key(const int *g, int K) {
     }
     s[b + 1] = v;
   }
-  return rank_genotype(s, K);
+}
+// Key of a genotype in the likelihood table of call_mcmc_kernel<KM>.  The instantiation for ploidies up to 8 keeps the exact
+// caller's rank_genotype: it runs over at most CALL_MAX_HAPS = 256 haplotypes, C(263, 8) < 2^48.9 genotypes, and cwr's largest
+// intermediate is eight times the count -- below 2^52.  The instantiation for ploidies 9 to 15 reaches 2^62 genotypes and
+// takes call_rank.
+template <int KM>
+__device__ __forceinline__ long long call_key(const int *g, int K) {
+  int s[EXACT_KMAX];
+  call_sorted(g, K, s);
+  if constexpr (KM <= 8) return rank_genotype(s, K);
+  else return call_rank(s, K);
+}
+// ... and in that of call_wide_kernel<KM> (call_wide_kernel.hpp: here, so that the parity suite's library can reach it)
+template <int KM>
+__device__ __forceinline__ long long call_wide_key(const int *g, int K) {
+  int s[KM];
+  call_sorted(g, K, s);
+  return call_rank(s, K);
 }
 
 // Key of a Gibbs context over at most sixteen known haplotypes: how many copies of each the other K - 1 <= 7 alleles hold, four
@@ -462,7 +498,7 @@ __global__ __launch_bounds__(64 * CALL_WG_CHAINS, 2) void call_mcmc_kernel(const
     bool miss = false;
     long long key = 0;
     if (act) {
-      key = call_key(g, K);
+      key = call_key<KM>(g, K);
       miss = !probe(key, val, slot);
       if (miss && !slot) s_full = 1;
     }
@@ -532,7 +568,7 @@ __global__ __launch_bounds__(64 * CALL_WG_CHAINS, 2) void call_mcmc_kernel(const
         if (has_prior) cur_lprior = calling_log_prior_unsorted(pt, g, K);
         double val = 0.0;
         ulonglong2 *slot = nullptr;
-        const long long key = call_key(g, K);
+        const long long key = call_key<KM>(g, K);
         bool hit = false;
         if (lane == 0) {
           hit = probe(key, val, slot);

@@ -118,35 +118,7 @@ __global__ __launch_bounds__(CALL_WIDE_SETUP_THREADS) void call_wide_setup_kerne
   }
 }
 
-// C(n + k - 1, k) without an intermediate beyond the result (cwr of exact_kernel.hpp forms r * (n - 1 + d) before it divides: over
-// a thousand haplotypes that product can pass 2^63 where the count itself stays below 2^62).  The same values.
-__device__ __forceinline__ long long call_wide_cwr(int n, int k) {
-  if (n <= 0) return 0;
-  long long r = 1;
-  for (int d = 1; d <= k; d++) {
-    const long long m = n - 1 + d;
-    r = (r / d) * m + ((r % d) * m) / d;
-  }
-  return r;
-}
-template <int KM>
-__device__ __forceinline__ long long call_wide_key(const int *g, int K) {
-  int s[KM];
-  for (int i = 0; i < K; i++) s[i] = g[i];
-  for (int a = 1; a < K; a++) {  // insertion sort
-    const int v = s[a];
-    int b = a - 1;
-    while (b >= 0 && s[b] > v) {
-      s[b + 1] = s[b];
-      b--;
-    }
-    s[b + 1] = v;
-  }
-  long long idx = 0;  // jitutils.py:253-276
-  for (int i = 0; i < K; i++) idx += call_wide_cwr(s[i], i + 1);
-  return idx;
-}
-
+// (the keys of the likelihood table: call_wide_key -> call_rank, call_mcmc_kernel.hpp)
 template <int KM = 8>
 __global__ __launch_bounds__(64 * CALL_WG_CHAINS) void call_wide_kernel(const CallWideParams W) {
   extern __shared__ __align__(16) unsigned char smem[];

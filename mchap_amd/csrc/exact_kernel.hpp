@@ -49,7 +49,12 @@ struct ExactParams {
   double *part_freq;            // [U][nblk][2H + 1]: allele counts, allele occurrence, mode-support probability
 };
 
-// C(n + k - 1, k), the number of genotypes of ploidy k over n alleles (jitutils.py:228-250; 0 for n == 0)
+// C(n + k - 1, k), the number of genotypes of ploidy k over n alleles (jitutils.py:228-250; 0 for n == 0).
+// The product r * (n - 1 + d) is formed before the division: it is d times the next partial count, at most 15 times the result, so
+// the value is right while the count stays below 2^59.  The exact caller asks for cwr(n, p) with n <= H, p <= K alone (unrank_genotype,
+// rank_genotype) and ENUMERATES its C(H + K - 1, K) genotypes: its workspace holds four doubles per 4096 of them and a pass
+// visits each, so a count near 2^59 (2^50 bytes, years of passes) is out of its reach long before the arithmetic is.  The
+// call sampler ranks single genotypes of shapes up to 2^62: its keys take call_rank (call_mcmc_kernel.hpp) above ploidy 8.
 __device__ __forceinline__ long long cwr(int n, int k) {
   if (n <= 0) return 0;
   long long r = 1;

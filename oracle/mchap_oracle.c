@@ -231,22 +231,18 @@ void orc_increment_genotype(int64_t *g, int ploidy) {
 }
 
 /* jitutils.py:195-210 _comb */
-static int64_t gcd64(int64_t x, int64_t y) {
-  while (y != 0) { int64_t t = x % y; x = y; y = t; }
-  return x;
-}
+/* exact for every result below 2^63: the running value is a binomial coefficient itself (never above the result once k is
+ * folded to min(k, n - k)), and its product with the next factor is formed in 128 bits before the division */
 static int64_t comb64(int64_t n, int64_t k) {
   if (n < 0 || k < 0) return -1;
   if (k > n) return 0;
-  int64_t r = 1;
+  if (k > n - k) k = n - k;
+  unsigned __int128 r = 1;
   for (int64_t d = 1; d <= k; d++) {
-    int64_t g = gcd64(r, d);
-    r /= g;
-    r *= n;
-    r /= d / g;
+    r = r * (unsigned __int128)n / (unsigned __int128)d;
     n -= 1;
   }
-  return r;
+  return (int64_t)r;
 }
 
 /* jitutils.py:228-250 */
@@ -1613,6 +1609,7 @@ typedef struct {
   double inbreeding;
   const double *frequencies;
   call_cache *cache; /* nullable */
+  double *work;      /* [4 * n_haps]: a sub-step's joint / proposal terms, then the compound step's llks, lpriors, probabilities */
 } call_ctx;
 
 /* calling/likelihood.py:36-78 */
@@ -1638,7 +1635,7 @@ static double call_genotype_prior(const call_ctx *c, const int64_t *g) {
 static void gibbs_options(const call_ctx *c, int64_t *g, int k, double *llks, double *lpriors, double *probs) {
   const int64_t current = g[k];
   const int H = c->n_haps;
-  double joint[256];
+  double *joint = c->work;
   for (int a = 0; a < H; a++) {
     g[k] = a;
     lpriors[a] = orc_log_genotype_allele_prior(g, c->ploidy, k, H, c->has_prior, c->inbreeding, c->frequencies);
@@ -1656,7 +1653,7 @@ static void mh_options(const call_ctx *c, int64_t *g, int k, double *llks, doubl
   const int copies = count_allele(g, c->ploidy, g[k]);
   const double lprior = call_genotype_prior(c, g);
   const double llk = call_llk(c, g);
-  double lprop[256];
+  double *lprop = c->work;
   for (int a = 0; a < H; a++) {
     if (g[k] == a) { /* g[k] is reset to `current` only at the end: the comparison is against the running value */
       lprop[a] = 0.0;
@@ -1685,12 +1682,15 @@ int orc_call_step_options(const double *reads, int n_reads, int n_pos, int max_a
                           const int8_t *haplotypes, int n_haps, const int64_t *genotype, int ploidy, int variable_allele,
                           int step_type, int has_prior, double inbreeding, const double *frequencies, double *llks,
                           double *lpriors, double *probs) {
-  if (ploidy > ORC_MAX_PLOIDY || n_pos > ORC_MAX_POS || n_haps > 256) return ORC_ERR_LIMIT;
-  call_ctx c = {reads, n_reads, n_pos, max_allele, read_counts, haplotypes, n_haps, ploidy, has_prior, inbreeding, frequencies, NULL};
+  if (ploidy > ORC_MAX_PLOIDY || n_pos > ORC_MAX_POS) return ORC_ERR_LIMIT;
+  double *work = (double *)malloc(sizeof(double) * (size_t)(n_haps > 0 ? n_haps : 1));
+  if (!work) return ORC_ERR_LIMIT;
+  call_ctx c = {reads, n_reads, n_pos, max_allele, read_counts, haplotypes, n_haps, ploidy, has_prior, inbreeding, frequencies, NULL, work};
   int64_t g[ORC_MAX_PLOIDY];
   memcpy(g, genotype, sizeof(int64_t) * (size_t)ploidy);
   if (step_type == 0) gibbs_options(&c, g, variable_allele, llks, lpriors, probs);
   else mh_options(&c, g, variable_allele, llks, lpriors, probs);
+  free(work);
   return ORC_OK;
 }
 
@@ -1724,7 +1724,7 @@ int orc_greedy_caller(const double *reads, int n_reads, int n_pos, int max_allel
 /* calling/mcmc.py:232-327 */
 static double call_compound_step(const call_ctx *c, orc_rng *rng, int64_t *g, int step_type) {
   const int K = c->ploidy, H = c->n_haps;
-  double llks[256], lpriors[256], probs[256];
+  double *llks = c->work + H, *lpriors = llks + H, *probs = lpriors + H;
   int order[ORC_MAX_PLOIDY];
   for (int i = 0; i < K; i++) order[i] = i;
   for (int i = K - 1; i >= 1; i--) { /* np.random.shuffle(order) */
@@ -1749,8 +1749,10 @@ int orc_call_mcmc(const double *reads, int n_reads, int n_pos, int max_allele, c
                   const int8_t *haplotypes, int n_haps, int ploidy, int has_prior, double inbreeding,
                   const double *frequencies, int steps, int chains, int step_type, const int64_t *initial, int rng_kind,
                   uint64_t seed, uint64_t stream_id, int64_t *genotypes_out, double *llks_out) {
-  if (ploidy > ORC_MAX_PLOIDY || n_pos > ORC_MAX_POS || n_haps > 256) return ORC_ERR_LIMIT;
+  if (ploidy > ORC_MAX_PLOIDY || n_pos > ORC_MAX_POS) return ORC_ERR_LIMIT;
   if (step_type != 0 && step_type != 1) return ORC_ERR_BAD_ARG;
+  double *work = (double *)malloc(sizeof(double) * 4 * (size_t)(n_haps > 0 ? n_haps : 1)); /* one allocation for the call: the option arrays of every sub-step */
+  if (!work) return ORC_ERR_LIMIT;
   int64_t init[ORC_MAX_PLOIDY];
   if (initial) memcpy(init, initial, sizeof(int64_t) * (size_t)ploidy);
   else orc_greedy_caller(reads, n_reads, n_pos, max_allele, read_counts, haplotypes, n_haps, ploidy, has_prior, inbreeding, frequencies, init);
@@ -1766,7 +1768,7 @@ int orc_call_mcmc(const double *reads, int n_reads, int n_pos, int max_allele, c
     rng.mt = &mt;
     call_cache cache;
     call_cache_init(&cache);
-    call_ctx c = {reads, n_reads, n_pos, max_allele, read_counts, haplotypes, n_haps, ploidy, has_prior, inbreeding, frequencies, &cache};
+    call_ctx c = {reads, n_reads, n_pos, max_allele, read_counts, haplotypes, n_haps, ploidy, has_prior, inbreeding, frequencies, &cache, work};
     int64_t g[ORC_MAX_PLOIDY];
     memcpy(g, init, sizeof(int64_t) * (size_t)ploidy);
     for (int s = 0; s < steps; s++) {
@@ -1776,5 +1778,6 @@ int orc_call_mcmc(const double *reads, int n_reads, int n_pos, int max_allele, c
     }
     call_cache_free(&cache);
   }
+  free(work);
   return ORC_OK;
 }

@@ -1,4 +1,6 @@
 """Inputs of the tests of `mchap call` over many known haplotypes (tests/test_call_wide.py, tests/test_gpu_call_wide.py)."""
+import math
+
 import numpy as np
 
 
@@ -54,3 +56,27 @@ def wide_vcf(base_path, out_path, wide_records, seed=7):
         out.append(ln)
     with open(out_path, "w") as fh:
         fh.write("\n".join(out) + "\n")
+
+
+def largest_haps_below_2_62(K):
+    """the most haplotypes whose genotypes of ploidy K number less than 2^62 (the library's shape rule)"""
+    lo, hi = 1, 1 << 32  # (bisection: 3 037 000 500 haplotypes at ploidy 2)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if math.comb(mid + K - 1, K) < 1 << 62:
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def rank_cases(K, H, n_random=300, seed=0):
+    """sorted genotypes [n, K] over H haplotypes: the top one, the all-zero one, one allele apart from either, random ones over all
+    alleles and random ones among the top few -- with their exact VCF indices as Python integers"""
+    rng = np.random.default_rng(seed + 1000 * K + H)
+    g = [np.full(K, H - 1), np.zeros(K, np.int64), np.append(np.zeros(K - 1, np.int64), H - 1), np.append(np.full(K - 1, H - 2), H - 1)]
+    g += list(rng.integers(0, H, size=(n_random, K)))
+    g += list(rng.integers(max(0, H - 8), H, size=(n_random // 4, K)))
+    g = np.sort(np.array(g, dtype=np.int64), axis=1)
+    exact = [sum(math.comb(int(a) + i, i + 1) for i, a in enumerate(row)) for row in g]
+    return g, exact

@@ -1,7 +1,8 @@
 """Differential soak of the `mchap call` sampler (call_mcmc_kernel + call_coast_kernel) against the oracle on random shapes:
 ploidy 1-8 (and 9-12 without the Gibbs memo), 2-70 known haplotypes, 1-400 reads of mixed quality, 1-5 chains, both step types,
 with and without a prior / frequencies / read counts / an initial genotype, at random lanes per wavefront of the coast kernel.
-Needs a GPU; uses the oracle, hence lives under tests/ (tools/ never imports it).  python tests/fuzz_call.py [cases] [seed]"""
+With `--wide` the shapes are call_wide_kernel's on the default dispatch: 257-600 known haplotypes over 10-12 SNVs, ploidy 2-6.
+Needs a GPU; uses the oracle, hence lives under tests/ (tools/ never imports it).  python tests/fuzz_call.py [--wide] [cases] [seed] [case] [lanes]"""
 import os
 import sys
 
@@ -10,7 +11,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(n_cases, seed, only=None, lanes_override=None):
+def run(n_cases, seed, only=None, lanes_override=None, wide=False):
     from oracle import binding as orc
 
     from mchap_amd.calling_mcmc import CallingMCMC
@@ -27,6 +28,12 @@ def run(n_cases, seed, only=None, lanes_override=None):
         steps = int(rng.choice([30, 120, 500]))
         step_type = "Gibbs" if rng.random() < 0.8 else "Metropolis-Hastings"
         qual = (2, 8) if rng.random() < 0.4 else (5, 30)
+        if wide:  # (draws of their own, after the others: the sequences of the plain seeds stay what they were)
+            K = int(rng.choice([2, 3, 4, 5, 6]))
+            M = int(rng.integers(10, 13))
+            H = int(rng.integers(257, 601))
+            R = int(rng.choice([3, 12, 40]))
+            steps = int(rng.choice([20, 40]))
         U = 3
         # (a few reads cover every position: a position no read covers makes pairs of known haplotypes equally likely, and which of
         # two sums that differ in their last bit is the larger is not something two implementations agree on -- seed 24, case 101
@@ -87,7 +94,8 @@ def run(n_cases, seed, only=None, lanes_override=None):
 
 
 if __name__ == "__main__":
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 60
-    sd = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-    only = int(sys.argv[3]) if len(sys.argv) > 3 else None  # (one case of the sequence alone, optionally at other lanes: argv[4])
-    sys.exit(1 if run(n, sd, only, sys.argv[4] if len(sys.argv) > 4 else None) else 0)
+    args = [a for a in sys.argv[1:] if a != "--wide"]
+    n = int(args[0]) if len(args) > 0 else 60
+    sd = int(args[1]) if len(args) > 1 else 1
+    only = int(args[2]) if len(args) > 2 else None  # (one case of the sequence alone, optionally at other lanes: the fourth argument)
+    sys.exit(1 if run(n, sd, only, args[3] if len(args) > 3 else None, wide="--wide" in sys.argv[1:]) else 0)

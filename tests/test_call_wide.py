@@ -1,13 +1,17 @@
 """CPU: `mchap call` over more than 256 known haplotypes -- the library's bound and workspace figures (no device needed: they are
 plain functions of the shape), and the program `application.call` with the sampler stubbed: a record of 300 alternate alleles is
-called like its neighbours and leaves their lines alone, a record beyond mchap_call_mcmc_max_haps is a FILTER=LIMIT record."""
+called like its neighbours and leaves their lines alone, a record beyond mchap_call_mcmc_max_haps is a FILTER=LIMIT record.
+
+And the checker itself beyond 256 haplotypes: the oracle's sampler against the reference's own (tests/golden/call_wide_traces.npz,
+made by tests/golden/make_call_wide.py), its genotype counts and ranks against exact integers up to the 2^62 bound."""
 import io as _io
+import math
 import os
 
 import numpy as np
 import pytest
 
-from tests.call_wide_helpers import wide_vcf
+from tests.call_wide_helpers import largest_haps_below_2_62, rank_cases, wide_vcf
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data")
 DEEP = ["simple.sample1.deep.bam", "simple.sample2.deep.bam", "simple.sample3.deep.bam"]
@@ -105,3 +109,91 @@ def test_call_program_with_a_stubbed_sampler(tmp_path, monkeypatch, capsys):
     assert by["BEYOND"][6] == "LIMIT" and by["BEYOND"][9].split(":")[0] == "./././."
     assert "not called" in err and "FILTER=LIMIT" in err and str(top) in err
     assert [ln for ln in both if ln.split("\t")[2] != "BEYOND"] == wide
+
+
+# ---- the oracle beyond 256 known haplotypes, against the reference ----
+def _wide_case(z, i):
+    p = "c%d_" % i
+    K, F, has_f = z[p + "meta"]
+    prior = None if F < 0 else (float(F), z[p + "freqs"] if has_f else None)
+    counts = z[p + "counts"]
+    return p, int(K), prior, (None if counts.size == 0 else counts)
+
+
+def test_oracle_beyond_256_transition_vectors_and_greedy_caller(golden_dir):
+    """test_oracle_call_mcmc.py::test_transition_vectors_and_greedy_caller (its tolerances) over 300, 321 and 1024 haplotypes, at
+    states whose alleles lie above 255."""
+    from oracle import binding as orc
+
+    z = np.load(os.path.join(golden_dir, "call_wide_traces.npz"))
+    kinds = set()
+    for i in range(int(z["n_cases"])):
+        p, K, prior, counts = _wide_case(z, i)
+        haps, reads = z[p + "haps"], z[p + "reads"]
+        kinds.add((None if prior is None else prior[1] is not None, counts is not None))
+        assert len(haps) > 256 and (z[p + "states"][:, :K] > 255).any(axis=1).all()
+        for state, vec in zip(z[p + "states"], z[p + "vectors"]):
+            g, k = state[:K], int(state[K])
+            for st in (0, 1):
+                llks, lpri, probs = orc.call_step_options(reads, haps, g, k, st, counts, prior)
+                np.testing.assert_allclose(llks, vec[st][0], rtol=1e-12)
+                np.testing.assert_allclose(lpri, vec[st][1], rtol=1e-12, atol=1e-12, equal_nan=True)
+                np.testing.assert_allclose(probs, vec[st][2], rtol=1e-10, atol=1e-300, equal_nan=True)
+        assert orc.greedy_caller(reads, haps, K, counts, prior).tolist() == z[p + "greedy"].tolist()
+    # no prior, (F, None) and (F, freqs); with and without read counts
+    assert {k[0] for k in kinds} == {None, False, True} and {k[1] for k in kinds} == {False, True}
+
+
+def test_oracle_beyond_256_seeded_fits_step_for_step(golden_dir):
+    """test_oracle_call_mcmc.py::test_seeded_fits_step_for_step over the same cases: the reference's CallingMCMC.fit under numpy's
+    MT19937, both step types and a fit from a given initial genotype -- alleles equal, llks to 1e-10.  The fixture's traces visit
+    alleles above 255 and change genotype, each step type's (or they would pin nothing that 256 haplotypes do not)."""
+    from oracle import binding as orc
+
+    z = np.load(os.path.join(golden_dir, "call_wide_traces.npz"))
+    n = int(z["n_cases"])
+    steps, chains, ini_steps, mh_steps = (int(v) for v in z["steps"])
+    shapes = set()
+    for i in range(n):
+        p, K, prior, counts = _wide_case(z, i)
+        haps, reads = z[p + "haps"], z[p + "reads"]
+        shapes.add((K, len(haps)))
+        beyond = 0
+        for st in (0, 1):
+            n_steps = mh_steps if st else steps  # (Metropolis-Hastings accepts few proposals: the fixture runs it longer)
+            ref_g, ref_l = z[p + "trace%d_g" % st], z[p + "trace%d_l" % st]
+            assert ref_g.shape == (chains, n_steps, K), (i, st)
+            assert (ref_g[:, 1:] != ref_g[:, :-1]).any(), (i, st)  # each step type's trace changes genotype
+            beyond += int((ref_g > 255).sum())
+            g, l = orc.call_mcmc(reads, haps, K, steps=n_steps, chains=chains, step_type=st, read_counts=counts, prior=prior,
+                                 rng_kind=orc.RNG_NUMPY_MT, seed=100 + i)
+            assert np.array_equal(g, ref_g), (i, st)
+            np.testing.assert_allclose(l, ref_l, rtol=1e-10)
+        # (per case, not per step type: a Metropolis-Hastings chain of a diploid may sit below 256 throughout, while every one of its
+        # sub-steps still prices all the options above 255)
+        assert beyond > 0, i
+        g, l = orc.call_mcmc(reads, haps, K, steps=ini_steps, chains=1, step_type=0, read_counts=counts, prior=prior,
+                             initial=z[p + "initial"], rng_kind=orc.RNG_NUMPY_MT, seed=7 + i)
+        assert (z[p + "initial"] > 255).any()  # (the start: the first sub-steps price options against an allele beyond 255)
+        assert np.array_equal(g, z[p + "trace_ini_g"]), i
+        np.testing.assert_allclose(l, z[p + "trace_ini_l"], rtol=1e-10)
+    assert {(4, 300), (3, 321), (2, 1024)} <= shapes
+
+
+def test_oracle_genotype_counts_and_ranks_up_to_the_bound():
+    """orc_comb_with_replacement and orc_genotype_alleles_as_index against math.comb for every ploidy 2 to 15 at the largest number
+    of haplotypes the 2^62 rule admits, and at the shapes the GPU tests of the wide path use."""
+    from oracle import binding as orc
+
+    shapes = [(largest_haps_below_2_62(K), K) for K in range(2, 16)] + [(806, 8), (1024, 7), (4096, 5), (300, 10), (105, 15), (4096, 2)]
+    assert (806, 8) in shapes[:14] and (105, 15) in shapes[:14]
+    for H, K in shapes:
+        G = math.comb(H + K - 1, K)
+        assert G < 1 << 62
+        assert orc.comb_with_replacement(H, K) == G, (H, K)
+        for k in range(1, K + 1):
+            assert orc.comb_with_replacement(H, k) == math.comb(H + k - 1, k), (H, k)
+        g, exact = rank_cases(K, H)
+        assert exact[0] == G - 1 and exact[1] == 0
+        for row, e in zip(g, exact):
+            assert orc.genotype_alleles_as_index(row) == e, (H, K, row.tolist())

@@ -1,18 +1,22 @@
 """GPU: `mchap call`'s sampler over many known haplotypes (call_wide_kernel behind CallingMCMC for more than 256 haplotypes, or
 for any number under MCHAP_HIP_CALL_WIDE=1).
 
-Where the oracle reaches (256 haplotypes, its own cap) the path is held to it on the same Philox streams -- alleles bit-exact step
-for step, llks to 1e-10 -- and to the default path's traces.  Beyond 256: determinism (status, sorted alleles, no dependence on
-the batch or on the chains per workgroup), the stationary distribution against the enumeration of all genotypes, and the program
-`mchap call` on a haplotype VCF with a record of 300 alternate alleles."""
+Up to 256 haplotypes the path is forced and held to the oracle on the same Philox streams -- alleles bit-exact step for step, llks
+to 1e-10 -- and to the default path's traces.  Beyond 256, where the kernel runs in production, the same on the default dispatch
+(the oracle's option arrays are sized by the haplotypes, and tests/test_call_wide.py holds it to the reference there): the
+smallest shapes at which a round of 64 lanes, a key, a table row or the workgroup's LDS carve can go wrong.  Then determinism
+(status, sorted alleles, no dependence on the batch or on the chains per workgroup), the stationary distribution against the
+enumeration of all genotypes, the keys' rank arithmetic against exact integers, and the program `mchap call` on a haplotype VCF
+with a record of 300 alternate alleles."""
 import io as _io
+import math
 import os
 
 import numpy as np
 import pytest
 
 from oracle import binding as orc
-from tests.call_wide_helpers import many_haplotypes, wide_vcf
+from tests.call_wide_helpers import largest_haps_below_2_62, many_haplotypes, rank_cases, wide_vcf
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_data")
@@ -48,7 +52,7 @@ def _both_paths(monkeypatch, model, *args, **kw):
     return default, wide
 
 
-# ---- 1. bit parity where the oracle reaches ----
+# ---- 1. the wide path forced at up to 256 haplotypes: the oracle's traces and the default path's ----
 @pytest.mark.parametrize("step_type", ["Gibbs", "Metropolis-Hastings"])
 @pytest.mark.parametrize("K,H,M,R,na", [(4, 6, 6, 40, None), (2, 9, 5, 20, None), (6, 5, 4, 70, None), (3, 12, 6, 130, None),
                                         (4, 18, 6, 1400, None),
@@ -98,7 +102,228 @@ def test_forced_wide_on_the_memo_shapes(shape, monkeypatch):
         assert np.array_equal(wide[u].genotypes, default[u].genotypes), u
 
 
-# ---- 2. beyond 256 ----
+# ---- 2. beyond 256: traces against the oracle on the default dispatch ----
+CALL_WIDE_LDS = 160 * 1024 - 1024  # call_wide_kernel.hpp: the dynamic LDS a workgroup may ask for, four arrays [H] of doubles a chain
+
+
+def _wg_chains(H, chains):
+    """mchap_call_wide_wg_chains restated (it is not exported): the chains of a unit that share a workgroup"""
+    wgc = min(chains, 4)
+    while wgc > 1 and wgc * 4 * H * 8 > CALL_WIDE_LDS:
+        wgc -= 1
+    return wgc
+
+
+def _wide_inputs(U, K, H, M, n_alleles=None):
+    if n_alleles is None:
+        return many_haplotypes(U, K, H, M, 12, seed=H + K, qual=(2, 8))
+    from tests.helpers import multiallelic_units
+
+    return multiallelic_units(np.random.default_rng(H + K), U, K, H, n_alleles, 12, qual=(2, 8), window=(2, len(n_alleles)))
+
+
+def _against_oracle(K, H, reads, haps, steps, chains, step_type, prior, counts, initial=None, seed=17):
+    """fit_batch on the default dispatch against orc.call_mcmc, unit by unit; returns the ORACLE's traces [U, chains, steps, K]"""
+    from mchap_amd.calling_mcmc import CallingMCMC
+
+    U = len(reads)
+    model = CallingMCMC(ploidy=K, haplotypes=haps[0], prior=None, steps=steps, chains=chains, random_seed=seed, step_type=step_type)
+    got = model.fit_batch(reads, counts, initial, haplotypes=haps, prior=prior)
+    want = []
+    for u in range(U):
+        pr = None if prior is None else (float(prior[0][u]), None if prior[1] is None else prior[1][u])
+        g, l = orc.call_mcmc(reads[u], haps[u], K, steps=steps, chains=chains, step_type=0 if step_type == "Gibbs" else 1,
+                             read_counts=None if counts is None else counts[u], prior=pr, initial=None if initial is None else initial[u],
+                             rng_kind=orc.RNG_PHILOX, seed=seed, stream_id=u)
+        assert np.array_equal(got[u].genotypes, g), (u, step_type, prior is None, counts is None)
+        np.testing.assert_allclose(got[u].llks, l, rtol=1e-10, atol=1e-9)
+        assert got[u].n_allele == H
+        want.append(g)
+    return np.array(want)
+
+
+def _moves(g):
+    return int((g[:, :, 1:] != g[:, :, :-1]).any(axis=-1).sum())
+
+
+WIDE_SHAPES = {  # K, H, M, steps, n_alleles
+    "H257": (4, 257, 10, 40, None),            # one lane in the fifth round
+    "H320": (3, 320, 10, 40, None),            # an exact multiple of 64
+    "H321": (3, 321, 10, 40, None),            # one lane past it
+    "H300": (4, 300, 10, 40, None),            # a partial last round
+    "H1024": (4, 1024, 12, 40, None),          # many rounds
+    "K7-H1024": (7, 1024, 12, 20, None),       # 2^57.7 genotypes
+    "K8-H806": (8, 806, 12, 20, None),         # the 2^62 bound itself
+    "H1273": (2, 1273, 12, 40, None),          # fewer than four chains fit a workgroup
+    "H4096": (2, 4096, 13, 12, None),          # one chain per workgroup
+    "K10-H300": (10, 300, 10, 20, None),       # the second instantiation, 2^60.7 genotypes
+    "A3-A4": (4, 300, 6, 40, [3, 4, 2, 3, 4, 3]),  # reads of three and four alleles per SNV
+}
+
+
+@pytest.mark.parametrize("step_type", ["Gibbs", "Metropolis-Hastings"])
+@pytest.mark.parametrize("shape", list(WIDE_SHAPES))
+def test_wide_traces_match_oracle_beyond_256(shape, step_type, monkeypatch):
+    """call_wide_kernel where it runs in production against the oracle: 2 units of distinct haplotype sets (3 chains; 2 at K >= 7 or
+    H >= 1024, 4 at H = 1273), without a
+    prior and counts, with (F, None) and with (F, freqs) and counts (F = 0, 0.12: F = 0 has its own branch), and once from a given
+    initial genotype.  The case is worth its name only if the ORACLE's chains move and visit alleles above 255: asserted."""
+    from mchap_amd import _lib
+
+    K, H, M, steps, na = WIDE_SHAPES[shape]
+    # (4 chains at H = 1273: three share a workgroup and the fourth runs alone; 2 where the oracle's own time is the test's)
+    U, chains = 2, 4 if shape == "H1273" else 2 if (K >= 7 or H >= 1024) else 3
+    monkeypatch.delenv("MCHAP_HIP_CALL_WIDE", raising=False)
+    monkeypatch.delenv("MCHAP_HIP_CALL_WIDE_CHAINS", raising=False)
+    assert H > 256 and H <= int(_lib.lib().mchap_call_mcmc_max_haps(K))
+    if shape == "H4096":
+        assert H == int(_lib.lib().mchap_call_mcmc_max_haps(2))
+    if shape == "K8-H806":
+        assert H == largest_haps_below_2_62(8)
+    assert _wg_chains(H, chains) == {"H1273": 3, "H4096": 1}.get(shape, chains)  # (H1273: fewer than its four chains; H4096: one)
+    reads, haps = _wide_inputs(U, K, H, M, na)
+    rng = np.random.default_rng(K * 1000 + H)
+    counts = rng.integers(1, 4, size=reads.shape[:2]).astype(np.int64)
+    F = np.array([0.0, 0.12, 0.3])[:U]
+    fr = rng.dirichlet(np.ones(H), size=U)
+    recorded = U * chains * (steps - 1)
+    moves, beyond = 0, 0
+    runs = [(prior, rc, None) for prior, rc in ((None, None), ((F, None), counts), ((F, fr), counts))]
+    runs.append(((F, fr), counts, np.sort(np.concatenate([rng.integers(0, H, size=(U, K - 1)), np.full((U, 1), H - 1)], axis=1), axis=1).astype(np.int64)))
+    for prior, rc, initial in runs:
+        g = _against_oracle(K, H, reads, haps, steps, chains, step_type, prior, rc, initial=initial)
+        assert (np.diff(g, axis=-1) >= 0).all() and g.max() < H
+        print("%s %s prior %s initial %s: %d moves of %d recorded steps, %d alleles above 255"
+              % (shape, step_type, prior is not None and (prior[1] is None and "F" or "F, freqs"), initial is not None, _moves(g), recorded, int((g > 255).sum())))
+        if step_type == "Gibbs":  # every run of the case: at least half of its recorded steps change genotype
+            assert 2 * _moves(g) >= recorded, (shape, _moves(g), recorded)
+        moves += _moves(g)
+        beyond += int((g > 255).sum())
+    assert beyond > 0, shape
+    assert moves >= 2, (shape, moves)  # (Metropolis-Hastings: at least twice per case)
+
+
+def test_wide_chains_over_more_than_one_workgroup(monkeypatch):
+    """K = 4 over 300 haplotypes with 1, 4, 5 and 9 chains (5 and 9: a unit's chains in more than one workgroup, the last one
+    partly filled), and again with one chain per workgroup: the oracle's traces each time."""
+    K, H, M, steps, U = 4, 300, 10, 40, 2
+    reads, haps = _wide_inputs(U, K, H, M)
+    prior = (np.array([0.0, 0.12]), None)
+    monkeypatch.delenv("MCHAP_HIP_CALL_WIDE", raising=False)
+    for forced in (None, "1"):
+        if forced is None:
+            monkeypatch.delenv("MCHAP_HIP_CALL_WIDE_CHAINS", raising=False)
+        else:
+            monkeypatch.setenv("MCHAP_HIP_CALL_WIDE_CHAINS", forced)
+        for chains in (1, 4, 5, 9):
+            for step_type in ("Gibbs", "Metropolis-Hastings"):
+                g = _against_oracle(K, H, reads, haps, steps, chains, step_type, prior, None)
+                assert (g > 255).any() and _moves(g) >= (2 if step_type != "Gibbs" else (U * chains * (steps - 1)) // 2)
+    monkeypatch.delenv("MCHAP_HIP_CALL_WIDE_CHAINS", raising=False)
+
+
+def test_one_haplotype_past_the_genotype_bound_is_refused_by_name():
+    from mchap_amd.calling_mcmc import CallingMCMC
+
+    H = largest_haps_below_2_62(8) + 1
+    assert H == 807
+    reads, haps = many_haplotypes(1, 8, H, 12, 8, seed=3)
+    with pytest.raises(NotImplementedError, match="2\\^62"):
+        CallingMCMC(ploidy=8, haplotypes=haps[0], steps=10, chains=1, random_seed=1).fit(reads[0])
+
+
+# ---- 3. the keys' rank arithmetic on the device ----
+# the lowest top allele (0-based) from which cwr's product r * (n - 1 + d) passes 2^63 at a shape the 2^62 rule admits
+CWR_OVERFLOWS_FROM = {11: 205, 12: 159, 13: 128, 14: 107, 15: 92}
+
+
+def _device_keys(g, which):
+    """mchap_debug_call_keys (the parity suite's library): which = 0 / 1 call_key<8> / <16>, 2 / 3 call_wide_key<8> / <16>"""
+    import ctypes as C
+
+    from mchap_amd import _lib
+
+    os.environ["MCHAP_HIP_TEST_KERNELS"] = "1"
+    try:
+        L = _lib.lib()
+        f = L.mchap_debug_call_keys
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        g32 = np.ascontiguousarray(g, dtype=np.int32)
+        out = np.full(len(g32), -1, np.int64)
+        rc = f(g32.ctypes.data, len(g32), g32.shape[1], which, out.ctypes.data)
+        assert rc == 0, L.mchap_last_error().decode()
+    finally:
+        os.environ.pop("MCHAP_HIP_TEST_KERNELS", None)
+    return out
+
+
+@pytest.mark.parametrize("K", range(2, 16))
+def test_device_keys_are_the_exact_ranks(K):
+    """call_key (call_mcmc_kernel, up to 256 haplotypes) and call_wide_key (call_wide_kernel, up to 4096) on the device against exact
+    Python integers: the genotypes of tests/test_call_wide.py's rank test at the largest shape each kernel and the 2^62 rule admit,
+    and at ploidies 11 to 15 genotypes whose top allele is at or above the point where the product-before-division form overflows.
+    Integers: no tolerance."""
+    rng = np.random.default_rng(K)
+    km = 0 if K <= 8 else 1
+    for which, top in ((km, 256), (2 + km, 4096)):
+        H = min(top, largest_haps_below_2_62(K))
+        # (the largest shape is (806, 8), (105, 15), ... itself, and (4096, 5) on the wide key; two more shapes of the CPU test lie below it)
+        sets = [rank_cases(K, H)] + [rank_cases(K, h) for h in {7: [1024], 10: [300]}.get(K, []) if h <= H]
+        if K in CWR_OVERFLOWS_FROM:
+            lo = CWR_OVERFLOWS_FROM[K]
+            assert lo < H
+            g = np.sort(np.concatenate([rng.integers(0, H, size=(200, K - 1)), rng.integers(lo, H, size=(200, 1))], axis=1), axis=1)
+            g = np.concatenate([g, np.sort(rng.integers(lo, H, size=(100, K)), axis=1), [np.append(np.zeros(K - 1, np.int64), lo)]])
+            sets.append((g, [sum(math.comb(int(a) + i, i + 1) for i, a in enumerate(row)) for row in g]))
+        for g, exact in sets:
+            assert max(exact) < 1 << 62
+            shuffled = rng.permuted(g, axis=1)  # (the keys sort their alleles themselves)
+            got = _device_keys(shuffled, which)
+            bad = [i for i in range(len(g)) if int(got[i]) != exact[i]]
+            assert not bad, (which, H, len(bad), g[bad[0]].tolist(), int(got[bad[0]]), exact[bad[0]])
+
+
+def test_device_summaries_of_wide_traces_equal_the_host_classes():
+    """test_gpu_call_mcmc.py::test_device_summaries_of_call_traces_equal_the_host_classes over 300 haplotypes at ploidy 4, what the
+    program reads off call_wide_kernel's traces: two units of 3 poor reads (900 steps x 3 chains: more than 512 distinct genotypes,
+    the listed launch) and a settled unit of 200 good reads in one batch (the poor units' reads padded with all-NaN rows, which
+    add nothing to a likelihood).  Every assertion of that test but the GP array: as_array(300) at ploidy 4 is
+    C(303, 4) = 3.4e8 doubles."""
+    from mchap_amd.calling_mcmc import CallingMCMC
+
+    K, H, M, steps, chains, R = 4, 300, 10, 900, 3, 200
+    poor, haps_p = many_haplotypes(2, K, H, M, 3, seed=41, qual=(2, 6))
+    good, haps_g = many_haplotypes(1, K, H, M, R, seed=43)
+    reads = np.full((3, R) + poor.shape[2:], np.nan)
+    reads[:2, :3] = poor
+    reads[2] = good[0]
+    haps = np.concatenate([haps_p, haps_g])
+    U, burn = 3, steps // 3
+    model = CallingMCMC(ploidy=K, haplotypes=haps[0], prior=None, steps=steps, chains=chains, random_seed=29)
+    kw = dict(haplotypes=haps, prior=(np.full(U, 0.15), None))
+    got = model.fit_batch_summaries(reads, None, burn=burn, incongruence_threshold=0.6, **kw)
+    traces = model.fit_batch(reads, None, **kw)
+    sizes = []
+    for u in range(U):
+        tr = traces[u].burn(burn)
+        post = tr.posterior()
+        assert np.array_equal(got[u].genotypes, post.genotypes), u
+        np.testing.assert_array_equal(got[u].counts / got[u].n_obs, post.probabilities)
+        alleles, gprob, sprob = post.mode(genotype_support=True)
+        assert np.array_equal(got[u].alleles, alleles) and abs(got[u].gprob - gprob) < 1e-15 and abs(got[u].sprob - sprob) < 1e-12
+        assert got[u].mci == tr.replicate_incongruence(threshold=0.6)
+        for a, b in zip(got[u].posterior_frequencies(), tr.posterior_frequencies()):
+            assert len(a) == H
+            np.testing.assert_array_equal(a, b)
+        labels = np.arange(H) * 2 + 1
+        np.testing.assert_array_equal(got[u].relabel(labels).posterior_frequencies()[2], tr.relabel(labels).posterior_frequencies()[2])
+        sizes.append(len(post.probabilities))
+    print("distinct genotypes per unit:", sizes)
+    assert max(sizes[:2]) > 512 and sizes[2] < 64, sizes
+    assert (np.asarray(traces[0].genotypes) > 255).any()
+
+
+# ---- 4. beyond 256: determinism, the stationary distribution, the program ----
 @pytest.mark.parametrize("step_type", ["Gibbs", "Metropolis-Hastings"])
 @pytest.mark.parametrize("H", [300, 1024])
 def test_beyond_256_runs_and_is_deterministic(H, step_type, monkeypatch):

@@ -50,3 +50,11 @@ def test_exact_caller_random_shapes_match_oracle(seed):
     import fuzz_exact
 
     assert fuzz_exact.run(12, seed, verbose=True) == 0
+
+
+def test_call_sampler_random_wide_shapes_match_oracle():
+    """The call sampler on random shapes of 257 to 600 known haplotypes (call_wide_kernel on the default dispatch; tests/fuzz_call.py
+    with `wide`): traces against the oracle.  Few cases: the whole test stays within seconds."""
+    import fuzz_call
+
+    assert fuzz_call.run(4, 61, wide=True) == 0
