@@ -2,15 +2,10 @@
 // Device pointers, a hipStream_t passed as void*, enqueue and return: the caller (mchap_amd/device.py) owns every buffer.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
 #include <cstdlib>
 
-#include "../../include/mchap_hip.h"
+#include "host_common.hpp"
 #include "call_reads_kernel.hpp"
-
-namespace mchap {
-int set_last_error(int code, const char *msg);
-}
 
 namespace {
 
@@ -29,10 +24,10 @@ int mchap_call_reads_from_calls_device(int n_units, const int8_t *calls, const i
                                        int64_t *read_counts, void *stream) {
   if (n_units <= 0) return MCHAP_OK;
   if (n_reads < 1 || n_pos < 1 || max_allele < 1)
-    return mchap::set_last_error(MCHAP_ERR_BAD_ARG, "call reads: n_reads, n_pos and max_allele must be at least 1");
+    return mchap::fail(MCHAP_ERR_BAD_ARG, "call reads: n_reads, n_pos and max_allele must be at least 1");
   // (calls / counts may be NULL when no unit has a row: they are then never read)
   if (!unit_rows || !unit_call_off || !unit_count_off || !n_alleles || !reads || !read_counts)
-    return mchap::set_last_error(MCHAP_ERR_BAD_ARG, "call reads: NULL buffer");
+    return mchap::fail(MCHAP_ERR_BAD_ARG, "call reads: NULL buffer");
   mchap::CallReadsParams P;
   P.calls = calls;
   P.counts = counts;
@@ -59,9 +54,7 @@ int mchap_call_reads_from_calls_device(int n_units, const int8_t *calls, const i
   hipLaunchKernelGGL(mchap::call_read_counts_kernel, dim3(grid_of(rows)), dim3(mchap::CALL_READS_THREADS), 0, (hipStream_t)stream, P);
   const hipError_t e = hipGetLastError();
   if (e == hipSuccess) return MCHAP_OK;
-  char buf[256];
-  snprintf(buf, sizeof(buf), "call_reads_kernel: %s", hipGetErrorString(e));
-  return mchap::set_last_error(MCHAP_ERR_HIP, buf);
+  return mchap::fail(MCHAP_ERR_HIP, "call_reads_kernel: %s", hipGetErrorString(e));
 }
 
 }  // extern "C"

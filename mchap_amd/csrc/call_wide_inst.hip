@@ -1,22 +1,24 @@
-// The `mchap call` sampler over many known haplotypes (call_wide_kernel.hpp) in its own object file.  The host API in
-// mchap_hip.hip (api_posterior_exact.inc) calls the entry points below; they are not part of the C ABI.  (The plain kernels of the
-// headers this object shares with mchap_hip.hip -- exact_mode_kernel, exact_freq_kernel, call_coast_kernel -- are `static` for its sake.)
+// The `mchap call` sampler over many known haplotypes (call_wide_kernel.hpp) in its own object file.  The host API in call_api.hip
+// calls the entry points below (call_wide_api.hpp); they are not part of the C ABI.  (The plain kernels of the headers this object
+// shares with others -- exact_mode_kernel and exact_freq_kernel, launched by exact_api.hip, and call_coast_kernel, launched by
+// call_api.hip -- are `static`: every object that includes their header compiles a copy of its own, and the copies do not clash.)
 #include <hip/hip_runtime.h>
 
 #include "../../include/mchap_hip.h"
+#include "call_wide_api.hpp"
 #include "call_wide_kernel.hpp"
 
 extern "C" {
 
-__attribute__((visibility("hidden"))) int mchap_call_wide_max_haps(void) { return mchap::CALL_WIDE_MAX_HAPS; }
+int mchap_call_wide_max_haps(void) { return mchap::CALL_WIDE_MAX_HAPS; }
 
 // bytes of a unit's tables in the workspace (a multiple of 256)
-__attribute__((visibility("hidden"))) int64_t mchap_call_wide_unit_bytes(int n_reads, int n_haps, int ploidy) {
+int64_t mchap_call_wide_unit_bytes(int n_reads, int n_haps, int ploidy) {
   return (int64_t)mchap::call_wide_unit_doubles(n_reads, n_haps, ploidy) * 8;
 }
 
 // chains of a unit per workgroup: as many as the LDS holds of their option arrays (MCHAP_HIP_CALL_WIDE_CHAINS, tests: fewer)
-__attribute__((visibility("hidden"))) int mchap_call_wide_wg_chains(int n_haps, int chains, int forced) {
+int mchap_call_wide_wg_chains(int n_haps, int chains, int forced) {
   int wgc = chains < mchap::CALL_WG_CHAINS ? chains : mchap::CALL_WG_CHAINS;
   while (wgc > 1 && mchap::call_wide_lds_bytes(n_haps, wgc) > mchap::CALL_WIDE_LDS) wgc--;
   if (forced >= 1 && forced < wgc) wgc = forced;
@@ -24,7 +26,7 @@ __attribute__((visibility("hidden"))) int mchap_call_wide_wg_chains(int n_haps, 
 }
 
 // the setup launch (the units' tables) and the sampler; unit_tab: n_units x mchap_call_wide_unit_bytes of the workspace
-__attribute__((visibility("hidden"))) int mchap_call_wide_launch(const mchap::CallParams *P, double *unit_tab, int wgc, hipStream_t stream) {
+int mchap_call_wide_launch(const mchap::CallParams *P, double *unit_tab, int wgc, hipStream_t stream) {
   mchap::CallWideParams W;
   W.c = *P;
   W.unit_tab = unit_tab;

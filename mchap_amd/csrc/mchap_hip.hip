@@ -11,7 +11,7 @@
 #include <mutex>
 #include <vector>
 
-#include "../../include/mchap_hip.h"
+#include "host_common.hpp"
 #include "denovo_kernel.hpp"
 #include "denovo_simt_kernel.hpp"
 #include "denovo_spec_kernel.hpp"
@@ -20,9 +20,6 @@
 #include "denovo_fill_kernel.hpp"
 #include "denovo_lane_kernel.hpp"
 #endif
-#include "exact_kernel.hpp"
-#include "call_mcmc_kernel.hpp"
-#include "posterior_kernel.hpp"
 
 // ---- sampler objects ------------------------------------------------------------------------------------------
 // Every instantiation of a sampler kernel is its own object file (spec_inst.hip, simt_inst.hip, ...: they compile in
@@ -115,7 +112,10 @@ thread_local char g_err[512] = "";
 // as before.
 std::atomic<uint64_t> g_cache_epoch{0};
 
-int fail(int code, const char *fmt, ...) {
+}  // namespace
+
+// (host_common.hpp: the one definition of the library -- the other host objects report their errors through it)
+int mchap::fail(int code, const char *fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
@@ -123,20 +123,13 @@ int fail(int code, const char *fmt, ...) {
   return code;
 }
 
-}  // namespace
-
-namespace mchap {
-// the error text of an entry point defined in another object of the library (pileup_inst.hip)
-int set_last_error(int code, const char *msg) { return fail(code, "%s", msg); }
-}  // namespace mchap
+using mchap::DevBuf;
+using mchap::ensure_init;
+using mchap::fail;
+using mchap::HostCall;
+using mchap::up256;
 
 namespace {
-
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) return fail(MCHAP_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 std::mutex g_init_mu;
 bool g_init_done[64] = {false};
@@ -185,7 +178,9 @@ const SpecInst *find_inst(const SpecInst *tab, size_t n, int K, int G) {
 #define ROW_SPECC(k) {mchap_specp_launchc_##k##_64, mchap_specs_launchc_##k##_64, mchap_specd_launchc_##k##_64},
 const simt_launch_fn SPECC_LAUNCH[7][3] = {ROW_SPECC(2) ROW_SPECC(3) ROW_SPECC(4) ROW_SPECC(5) ROW_SPECC(6) ROW_SPECC(7) ROW_SPECC(8)};
 
-int ensure_init() {
+}  // namespace
+
+int mchap::ensure_init() {
   int dev = 0;
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
@@ -226,62 +221,7 @@ int ensure_init() {
   return MCHAP_OK;
 }
 
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  template <class T>
-  T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-// A host-pointer entry point works on a stream of its own (non-blocking: it neither waits for nor stalls the caller's
-// other streams) and synchronises that stream only.
-struct HostCall {
-  hipStream_t stream = nullptr;
-  int open() {
-    HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    return MCHAP_OK;
-  }
-  ~HostCall() {
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-  int up(void *dst, const void *src, size_t bytes) {
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
-    return MCHAP_OK;
-  }
-  int down(void *dst, const void *src, size_t bytes) {
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
-    return MCHAP_OK;
-  }
-  int sync() {
-    HIP_TRY(hipStreamSynchronize(stream));
-    return MCHAP_OK;
-  }
-};
-#define MCHAP_TRY(expr)       \
-  do {                        \
-    const int rc_ = (expr);   \
-    if (rc_) return rc_;      \
-  } while (0)
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-// one device allocation for a host-pointer call: pieces handed out 256-byte aligned
-struct DevArena {
-  DevBuf buf;
-  size_t cap = 0, off = 0;
-  int reserve(size_t bytes) {
-    cap = bytes + 4096;
-    if (hipMalloc(&buf.p, cap) != hipSuccess) return fail(MCHAP_ERR_HIP, "hipMalloc of %zu bytes", cap);
-    return MCHAP_OK;
-  }
-  template <class T>
-  T *take(size_t n) {
-    T *p = reinterpret_cast<T *>(reinterpret_cast<unsigned char *>(buf.p) + off);
-    off += up256(n * sizeof(T));
-    return off <= cap ? p : nullptr;
-  }
-};
+namespace {
 
 // bytes per lane and row of the coded table: 1, 2, or a multiple of 4 (the sampler loads 1 / 2 / 4 bytes at a time)
 int code_stride(int rpl) { return rpl <= 2 ? rpl : (rpl + 3) & ~3; }
@@ -1008,46 +948,6 @@ int mchap_debug_pipe_memo(const mchap_denovo_cfg *cfg, int n_units, const mchap_
 }
 #endif
 
-#ifdef MCHAP_TEST_KERNELS
-/* test library only: the keys of the call sampler's likelihood tables, computed on the device.  genotypes: [n][ploidy] int32
- * alleles in any order (host); which = 0: call_key<8> (call_mcmc_kernel, ploidy <= 8), 1: call_key<16> (ploidies 9 to 15),
- * 2: call_wide_key<8>, 3: call_wide_key<16>; ranks: [n] int64 (host). */
-static __global__ __launch_bounds__(256) void debug_call_keys_kernel(const int *genotypes, int n, int K, int which, long long *ranks) {
-  for (int i = (int)threadIdx.x; i < n; i += (int)blockDim.x) {
-    int g[mchap::EXACT_KMAX];
-    for (int q = 0; q < mchap::EXACT_KMAX; q++) g[q] = q < K ? genotypes[(size_t)i * K + q] : 0;
-    long long r;
-    if (which == 0) r = mchap::call_key<8>(g, K);
-    else if (which == 1) r = mchap::call_key<mchap::EXACT_KMAX>(g, K);
-    else if (which == 2) r = mchap::call_wide_key<8>(g, K);
-    else r = mchap::call_wide_key<mchap::EXACT_KMAX>(g, K);
-    ranks[i] = r;
-  }
-}
-int mchap_debug_call_keys(const int32_t *genotypes, int n, int ploidy, int which, int64_t *ranks) {
-  if (n <= 0) return MCHAP_OK;
-  if (!genotypes || !ranks) return fail(MCHAP_ERR_BAD_ARG, "NULL buffer");
-  if (which < 0 || which > 3 || ploidy < 1 || ploidy > ((which & 1) ? MCHAP_MAX_PLOIDY_DENOVO : 8))
-    return fail(MCHAP_ERR_BAD_ARG, "key function %d at ploidy %d", which, ploidy);
-  int rc = ensure_init();
-  if (rc) return rc;
-  int *g_dev = nullptr;
-  long long *r_dev = nullptr;
-  HIP_TRY(hipMalloc(&g_dev, (size_t)n * ploidy * sizeof(int)));
-  hipError_t e = hipMalloc(&r_dev, (size_t)n * sizeof(long long));
-  if (e == hipSuccess) e = hipMemcpy(g_dev, genotypes, (size_t)n * ploidy * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(debug_call_keys_kernel, dim3(1), dim3(256), 0, 0, g_dev, n, ploidy, which, r_dev);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(ranks, r_dev, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost);
-  (void)hipFree(g_dev);
-  (void)hipFree(r_dev);
-  if (e != hipSuccess) return fail(MCHAP_ERR_HIP, "mchap_debug_call_keys: %s", hipGetErrorString(e));
-  return MCHAP_OK;
-}
-#endif
-
 int mchap_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1490,7 +1390,5 @@ int mchap_wave_sum_batch(const double *x, int64_t n_waves, double *out) {
   MCHAP_TRY(hc.down(out, d_o.p, (size_t)n_waves * 8));
   return hc.sync();
 }
-
-#include "api_posterior_exact.inc"
 
 }  // extern "C"

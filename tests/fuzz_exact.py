@@ -13,7 +13,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-# ---- the host's choice of kernel path (mchap_amd/csrc/api_posterior_exact.inc, exact_kernel.hpp), restated ----
+# ---- the host's choice of kernel path (mchap_amd/csrc/exact_api.hip, exact_kernel.hpp), restated ----
 EXACT_THREADS = 256
 EXACT_GENOS_PER_BLOCK = 4096
 

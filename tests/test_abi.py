@@ -64,3 +64,86 @@ def test_lds_and_workspace_sizing():
     cfg = DenovoMCMC(ploidy=4, n_alleles=[2] * 8, random_seed=1, kernel=1)._cfg(8)
     # the call's break table ((8 + 1) x 8 doubles, rounded to 256 B) + 1024 cache entries of 16 B per chain
     assert L.mchap_denovo_workspace_bytes(C.byref(cfg), 10, None) == 768 + 10 * 2 * 1024 * 16
+
+
+def _null_buffer_calls(L):
+    """One entry point of each host object of the library that reports errors, with one unit and NULL for a required buffer:
+    (object, the call, the error text as the parent of the split into objects reported it).  Each returns before it touches the
+    device."""
+    import ctypes as C
+
+    i64 = C.c_int64
+    return [
+        # mchap_exact_call_batch_device(n_units, reads, n_reads, n_pos, max_allele, read_counts, haplotypes, n_haps, ploidy, has_prior,
+        #                               inbreeding, frequencies, out, workspace, workspace_bytes, stream)
+        ("exact caller", lambda: L.mchap_exact_call_batch_device(1, None, 8, 3, 2, None, None, 4, 2, 0, None, None, None, None, i64(0), None),
+         b"NULL buffer"),
+        # mchap_call_mcmc_batch_device(n_units, reads, n_reads, n_pos, max_allele, read_counts, haplotypes, n_haps, ploidy, has_prior,
+        #                              inbreeding, frequencies, initial, stream_ids, steps, chains, step_type, seed, genotypes, llks,
+        #                              status, workspace, workspace_bytes, stream)
+        ("call sampler", lambda: L.mchap_call_mcmc_batch_device(1, None, 8, 3, 2, None, None, 4, 2, 0, None, None, None, None, 50, 2, 0,
+                                                                C.c_uint64(1), None, None, None, None, i64(0), None),
+         b"NULL buffer"),
+        # mchap_trace_posterior_batch_device(n_units, units, steps, chains, burn, trace_words, max_states, ploidy_max, post_words,
+        #                                    post_counts, post_n, mode_stats, mode_index, mode_words, mode_count, stream)
+        ("trace posterior", lambda: L.mchap_trace_posterior_batch_device(1, None, 10, 2, 0, None, 4, 4, None, None, None, None, None, None,
+                                                                         None, None),
+         b"NULL buffer"),
+        # mchap_pileup_overlap_device(bytes, n_bytes, segments, first, n_segments, n_positions, stream)
+        ("pileup", lambda: L.mchap_pileup_overlap_device(None, 0, None, None, 1, 1, None), b"pileup overlap: NULL buffer"),
+    ]
+
+
+@pytest.fixture(params=["", "1"], ids=["libmchap_hip", "libmchap_hip_test"])
+def either_library(request, monkeypatch):
+    from mchap_amd import _lib
+
+    _lib.build()
+    if request.param:
+        monkeypatch.setenv("MCHAP_HIP_TEST_KERNELS", request.param)
+    else:
+        monkeypatch.delenv("MCHAP_HIP_TEST_KERNELS", raising=False)
+    return _lib.lib()
+
+
+def test_every_host_object_reports_through_the_one_error_buffer(either_library):
+    """The exact caller, the call sampler, the trace summaries and the pileup are objects of their own; mchap_last_error reads one
+    buffer per library, and each of them writes it.  Before each call the buffer holds another object's text."""
+    import ctypes as C
+
+    from mchap_amd import _lib
+
+    L = either_library
+    for name, call, text in _null_buffer_calls(L):
+        if name == "pileup":  # (another object's error first: a unit list that is NULL, from the trace summaries)
+            assert L.mchap_trace_posterior_listed_device(1, None, None, 10, 2, 0, None, 4, 4, None, None, None, None, None, None, None,
+                                                         None) == _lib.ERR_BAD_ARG
+            assert L.mchap_last_error() == b"NULL unit list"
+        else:
+            assert L.mchap_pileup_filter_device(None, None, 1, 0, 0.0, 0, 0.0, 0, 0, None, None, None) == _lib.ERR_BAD_ARG
+            assert L.mchap_last_error() == b"pileup filter: NULL buffer or no samples"
+        assert call() == _lib.ERR_BAD_ARG, name
+        assert L.mchap_last_error() == text, name
+
+
+def test_the_two_libraries_keep_their_error_texts_apart(monkeypatch):
+    """libmchap_hip.so and libmchap_hip_test.so loaded in one process: an error raised through one leaves the other's
+    mchap_last_error as it was, whichever object of either raised it."""
+    from mchap_amd import _lib
+
+    _lib.build()
+    monkeypatch.delenv("MCHAP_HIP_TEST_KERNELS", raising=False)
+    A = _lib.lib()
+    monkeypatch.setenv("MCHAP_HIP_TEST_KERNELS", "1")
+    B = _lib.lib()
+    assert A is not B and A._name != B._name
+    for first, second in ((A, B), (B, A)):
+        for name, call, text in _null_buffer_calls(second):
+            # `first` holds a text no call of _null_buffer_calls produces ...
+            assert first.mchap_pileup_filter_device(None, None, 1, 0, 0.0, 0, 0.0, 0, 0, None, None, None) == _lib.ERR_BAD_ARG
+            kept = b"pileup filter: NULL buffer or no samples"
+            assert first.mchap_last_error() == kept
+            # ... and keeps it while every object of `second` fails
+            assert call() == _lib.ERR_BAD_ARG, name
+            assert second.mchap_last_error() == text, name
+            assert first.mchap_last_error() == kept, name

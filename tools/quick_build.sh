@@ -1,5 +1,5 @@
 #!/bin/bash
-# Development aid: rebuild only the named objects of a sampler library (e.g. "specs_4_64 specp_4_64 mchap_hip") and link it from
+# Development aid: rebuild only the named objects of a sampler library (e.g. "specs_4_64 specp_4_64 call_api") and link it from
 # them plus the objects that are already there (stale, but link-compatible while no shared struct changed).  A release build is
 # `make -j8` in mchap_amd/csrc.  Usage: bash tools/quick_build.sh [OBJ=obj_phases EXTRA=-DMCHAP_PHASES OUT=libmchap_hip_phases.so] name...
 cd "$(dirname "$0")/../mchap_amd/csrc" || exit 1
