@@ -460,6 +460,28 @@ int mchap_pileup_depth_device(const uint8_t *bytes, int64_t n_bytes, const int64
 int mchap_pileup_filter_device(const int32_t *depth, const int8_t *ref_index, int64_t n_rows, int n_samples, double maf, int64_t mad,
                                double ind_maf, int64_t ind_mad, int64_t min_ind, int32_t *flags, double *admf, void *stream);
 
+/* find-snvs genotype calls: per (row, sample) the posterior mode of the exact caller's model restricted to one position (reference
+ * calling/exact.py posterior_mode over single-position reads), from the tensors the pileup launches leave: depth [n_rows][n_samples][4],
+ * flags [n_rows] and admf [n_rows][4] as above.  A site is a row whose flag has bit 0; the record lists its reference allele and its
+ * kept alternates in VCF order.  The ENUMERATED alleles are the listed ones, without the reference when the row is REFMASKED (a masked
+ * reference is no candidate); m is their number, d_0 .. d_{m-1} the sample's depths on them (depth on other alleles is ignored).
+ * For the sample's ploidy K (ploidy [n_samples] int32 on the device, 1..MCHAP_MAX_PLOIDY_DENOVO) the genotypes are the multisets of K
+ * enumerated alleles in VCF genotype order, and
+ *   llk(g)   = sum over a with d_a > 0 of d_a log((c_a p_call + (K - c_a) p_other) / K), c_a the dosage of a in g;
+ *   prior(g) = flat over the genotypes when inbreeding[s] is NaN (inbreeding [n_samples] float64 on the device), else the reference's
+ *              calling/prior.py log_genotype_prior(g, m, inbreeding[s], frequencies): frequencies none (use_admf = 0) or the row's
+ *              admf over the enumerated alleles normalised to sum 1 (use_admf != 0; ignored for a sample whose inbreeding is NaN).
+ * gt_index [n_rows][n_samples] int32: the index among the genotypes over the m enumerated alleles of the first maximum of llk + prior;
+ * gpm [n_rows][n_samples] float64: its posterior probability exp(max - logsumexp) in float64.  gt_index = -1 and gpm = NaN for a row
+ * that is no site, and for a NO-CALL: the sample has no depth on the enumerated alleles; frequencies are in use and an enumerated
+ * allele's is 0 (AF0 of the call programs); no genotype has a likelihood above 0 (p_other = 0 and more alleles seen than K); an
+ * inbreeding outside [0, 1).  Each pair is computed by one lane alone: two runs give the same bits.
+ * Enqueues the launch on `stream` and does not wait for it; before that it reads the n_samples ploidies back (one wait on `stream`) to
+ * size the launch and to refuse a ploidy above MCHAP_MAX_PLOIDY_DENOVO (MCHAP_ERR_LIMIT) or below 1 (MCHAP_ERR_BAD_ARG). */
+int mchap_snv_genotypes_device(const int32_t *depth, const int32_t *flags, const double *admf, int64_t n_rows, int n_samples,
+                               const int32_t *ploidy, const double *inbreeding, int use_admf, double p_call, double p_other,
+                               int32_t *gt_index /*[n_rows][n_samples]*/, double *gpm /*[n_rows][n_samples]*/, void *stream);
+
 /* Introspection */
 const char *mchap_version(void);
 const char *mchap_last_error(void);

@@ -206,6 +206,8 @@ def lib():
                                                 C.c_int, C.c_void_p, C.c_void_p]
         L.mchap_pileup_filter_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_int64, C.c_double,
                                                  C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mchap_snv_genotypes_device.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int] + [C.c_void_p] * 2 + [C.c_int] + [C.c_double] * 2 + \
+            [C.c_void_p] * 3
         L.mchap_call_reads_from_calls_device.argtypes = [C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_double] * 2 + [C.c_void_p] * 3
         L.mchap_timer_ms.argtypes = [C.c_void_p]
         L.mchap_timer_destroy.argtypes = [C.c_void_p]
@@ -251,6 +253,7 @@ EXPORTS = [
     "mchap_pileup_overlap_device",
     "mchap_pileup_depth_device",
     "mchap_pileup_filter_device",
+    "mchap_snv_genotypes_device",
     "mchap_denovo_fit_batch_device",
     "mchap_denovo_fit_batch_calls_device",
     "mchap_denovo_fit_batch",

@@ -21,6 +21,15 @@ def _flag(p, name, dest, action, help):
     p.add_argument(name, dest=dest, action=action, default=(action == "store_false"), help=help)
 
 
+class _CallFlag(argparse._StoreAction):
+    """A --call-* flag of find-snvs: stored as usual, and its name noted in `call_flags` (a flag given with its default value
+    still counts as given)."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        super().__call__(parser, namespace, values, option_string)
+        namespace.call_flags = getattr(namespace, "call_flags", ()) + (option_string,)
+
+
 def _sample_args(p, dirmul_nargs):
     p.add_argument("--bam", type=str, nargs="+", default=[],
                    help="BAM / SAM file(s), a text file with one path per line, or a text file of sample<TAB>path lines")
@@ -73,6 +82,18 @@ def build_parser(program):
         _flag(p, "--keep-qcfail-reads", "skip_qcfail", "store_false", "count reads marked as qcfail")
         _flag(p, "--keep-supplementary-reads", "skip_supplementary", "store_false", "count reads marked as supplementary")
         p.add_argument("--cores", type=int, nargs=1, default=[1], help="host threads reading the alignment files")
+        # (not reference flags: the reference's find-snvs leaves every GT null)
+        p.add_argument("--call-genotypes", type=str, nargs=1, default=[None], metavar="PLOIDY", action=_CallFlag,
+                       help="call each sample's genotype from its allele depths (GT:GPM:AD): the ploidy of all samples, or a file of "
+                            "sample<TAB>ploidy lines")
+        p.add_argument("--call-inbreeding", type=str, nargs=1, default=[None], metavar="F", action=_CallFlag,
+                       help="with --call-genotypes: Dirichlet-multinomial prior with this inbreeding (0 <= F < 1), a value or a file "
+                            "of sample<TAB>value lines")
+        p.add_argument("--call-prior", type=str, nargs=1, default=["FLAT"], choices=["FLAT", "ADMF"], action=_CallFlag,
+                       help="with --call-genotypes: prior allele frequencies, FLAT or the record's ADMF; ADMF without --call-inbreeding "
+                            "means F = 0")
+        p.add_argument("--call-error-rate", type=float, nargs=1, default=[0.0024], action=_CallFlag,
+                       help="with --call-genotypes: base error rate")
         return p
     if program == "assemble":
         _sample_args(p, 1)
@@ -213,6 +234,27 @@ def run(argv, out=None):
     return n
 
 
+def find_snvs_call_settings(args, samples):
+    """The --call-* flags of find-snvs -> the `genotypes` settings of find_snvs.find_snvs, or None without --call-genotypes (any
+    other --call-* flag is then an error).  There is no prior unless --call-inbreeding or --call-prior ADMF is given."""
+    from . import io
+
+    if args.call_genotypes[0] is None:
+        for flag in getattr(args, "call_flags", ()):
+            raise ValueError("%s needs --call-genotypes" % flag)
+        return None
+    ploidy = io.sample_values(args.call_genotypes[0], samples, int)
+    inbreeding = io.sample_values(args.call_inbreeding[0], samples, float)
+    for name, values, ok in (("--call-genotypes", ploidy, lambda v: v >= 1), ("--call-inbreeding", inbreeding, lambda v: 0.0 <= v < 1.0)):
+        for v in (values.values() if isinstance(values, dict) else [] if values is None else [values]):
+            if not ok(v):
+                raise ValueError("%s: %r is out of range" % (name, v))
+    error_rate = args.call_error_rate[0]
+    if not 0.0 <= error_rate < 1.0:
+        raise ValueError("--call-error-rate must be in [0, 1)")
+    return dict(ploidy=ploidy, inbreeding=inbreeding, frequencies="ADMF" if args.call_prior[0] == "ADMF" else None, error_rate=error_rate)
+
+
 def _run_find_snvs(argv, args, out):
     """find-snvs: the header, then the records of every BED interval in file order (one process: sharding is out of scope)."""
     import os
@@ -233,10 +275,12 @@ def _run_find_snvs(argv, args, out):
     source = application.ReadSource(sample_bams, read_group_field=id_field, mapping_quality=args.mapping_quality[0],
                                     skip_duplicates=args.skip_duplicates, skip_qcfail=args.skip_qcfail,
                                     skip_supplementary=args.skip_supplementary, workers=args.cores[0])
+    genotypes = find_snvs_call_settings(args, list(sample_bams))
     records = find_snvs.find_snvs(targets, reference, source, maf=args.maf[0], mad=args.mad[0], ind_maf=args.ind_maf[0],
-                                  ind_mad=args.ind_mad[0], min_ind=args.min_ind[0])
+                                  ind_mad=args.ind_mad[0], min_ind=args.min_ind[0], genotypes=genotypes)
     lines = list(records)  # (errors -- an interval past its contig's end -- surface before any output)
-    for line in vcfheader.find_snvs_header_lines(["mchap_amd"] + list(argv[1:]), args.reference[0], list(sample_bams), reference.contigs):
+    for line in vcfheader.find_snvs_header_lines(["mchap_amd"] + list(argv[1:]), args.reference[0], list(sample_bams), reference.contigs,
+                                                 genotypes=genotypes is not None):
         out.write(line + "\n")
     for line in lines:
         out.write(line + "\n")

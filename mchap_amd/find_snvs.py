@@ -6,7 +6,8 @@ The per-base histogram over (position x sample x 4 bases) and the allele filter 
     to tiles of target rows, indexed CSR by (sample, tile);
   - the mate pairs of htslib's overlap rule and the reference positions both mates align a base to.
 Only the rows the filter keeps come back to the host.  Counting rule, and where it departs from the reference: DESIGN.md
-"find-snvs".  There is no CPU path: a missing library or device is an error."""
+"find-snvs".  Optionally (`genotypes=`, not in the reference) a fourth launch calls every sample's genotype at every record from the
+depth tensor (csrc/snv_genotype_kernel.hpp) and the records carry GT:GPM:AD.  There is no CPU path: a missing library or device is an error."""
 import ctypes as C
 import time
 
@@ -351,6 +352,58 @@ def decode_flags(flags):
     return (flags & 1).astype(bool), keep, order, ((flags >> 16) & 1).astype(bool)
 
 
+def genotypes_device(depth, flags, admf, ploidy, inbreeding=None, frequencies=None, error_rate=0.0024):
+    """Genotype calls over the tensors the depth and filter launches leave on the device (the rule: include/mchap_hip.h
+    mchap_snv_genotypes_device): depth int32 [P, S, 4], flags int32 [P], admf float64 [P, 4].  ploidy: one value or one
+    per sample; inbreeding: None (no prior unless frequencies are asked for, which then means 0), one value or one per sample
+    (NaN: no prior for that sample); frequencies: None or "ADMF".  -> (gt_index int32 [P, S], gpm float64 [P, S]) on the device:
+    the mode's index among the genotypes over the row's enumerated alleles and its posterior probability, -1 / NaN for a row that
+    is no record and for a no-call."""
+    import torch
+
+    from ._lib import check
+
+    _, L = _lib()
+    if frequencies not in (None, "ADMF"):
+        raise ValueError('frequencies must be None or "ADMF"')
+    if not 0.0 <= float(error_rate) < 1.0:
+        raise ValueError("error_rate must be in [0, 1)")
+    P, S = int(depth.shape[0]), int(depth.shape[1])
+    k = np.broadcast_to(np.asarray(ploidy, dtype=np.int64), (S,))
+    if inbreeding is None:
+        inbreeding = 0.0 if frequencies == "ADMF" else np.nan
+    F = np.broadcast_to(np.asarray(inbreeding, dtype=np.float64), (S,))
+    if ((F < 0) | (F >= 1)).any():
+        raise ValueError("inbreeding must be in [0, 1)")
+    depth, flags, admf = depth.contiguous(), flags.contiguous(), admf.contiguous()
+    d_k = torch.from_numpy(k.astype(np.int32)).to(depth.device)
+    d_F = torch.from_numpy(np.array(F, dtype=np.float64)).to(depth.device)
+    gt = torch.empty((P, S), dtype=torch.int32, device=depth.device)
+    gpm = torch.empty((P, S), dtype=torch.float64, device=depth.device)
+    p_call = 1.0 - float(error_rate)      # (as encoding.encode_read_distributions forms them)
+    p_other = (1.0 - p_call) / 3.0
+    check(L.mchap_snv_genotypes_device(_vp(depth), _vp(flags), _vp(admf), P, S, _vp(d_k), _vp(d_F), int(frequencies == "ADMF"),
+                                       C.c_double(p_call), C.c_double(p_other), _vp(gt), _vp(gpm),
+                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return gt, gpm
+
+
+def genotype_alleles(index, ploidy, refmasked=False):
+    """A genotype index over a record's enumerated alleles -> its `ploidy` alleles as VCF allele indices, ascending (the inverse
+    of VCF genotype order: index = sum_i C(a_i + i - 1, i) over the sorted alleles a_1 <= ... <= a_K).  On a REFMASKED record the
+    enumerated alleles start at the first alternate: every label is one higher."""
+    from math import comb
+
+    out, index = [], int(index)
+    for i in range(int(ploidy), 0, -1):
+        a = 0
+        while comb(a + i, i) <= index:
+            a += 1
+        index -= comb(a + i - 1, i)
+        out.append(a + (1 if refmasked else 0))
+    return out[::-1]
+
+
 # ---- record formatting (reference write_vcf_block and its helpers) ----------------------------------------------------
 def vcf_sort_alleles(frequencies, reference_index):
     """Reference _vcf_sort_alleles: argsort(stable) reversed, the reference allele moved first."""
@@ -393,9 +446,35 @@ def format_samples_columns(allele_depths, allele_keep):
     return np.concatenate([np.full((len(strings), 1), "GT:AD", dtype=dt), strings.astype(dt)], axis=1)
 
 
-def format_records(contigs, positions, depth, flags, admf):
+def format_genotype_columns(allele_depths, allele_keep, gt_index, gpm, ploidy, refmasked):
+    """format_samples_columns with calls: [n, 1 + S] = the FORMAT column "GT:GPM:AD" and one "<GT>:<GPM>:<AD>" per sample.  GT:
+    the mode's alleles as VCF indices, ascending, joined by "/" (`ploidy` dots for a no-call, gt_index < 0); GPM to 3 decimals."""
+    gt_index, gpm = np.asarray(gt_index, dtype=np.int64), np.asarray(gpm, dtype=np.float64)
+    n, S = gt_index.shape
+    ploidy = np.broadcast_to(np.asarray(ploidy, dtype=np.int64), (S,))
+    refmasked = np.asarray(refmasked, dtype=bool)
+    gt = np.empty((n, S), dtype=object)
+    for K in np.unique(ploidy):  # one table of genotype texts per (ploidy, masked): the last entry is the no-call
+        cols = np.flatnonzero(ploidy == K)
+        for masked in (False, True):
+            rows = np.flatnonzero(refmasked == masked)
+            if len(rows) == 0:
+                continue
+            g = gt_index[np.ix_(rows, cols)]
+            table = np.array(["/".join(map(str, genotype_alleles(i, K, masked))) for i in range(int(g.max(initial=-1)) + 1)] +
+                             ["/".join("." * int(K))], dtype=object)
+            gt[np.ix_(rows, cols)] = table[np.where(g < 0, len(table) - 1, g)]
+    values, inverse = np.unique(np.where(np.isnan(gpm), -1.0, gpm.round(3)), return_inverse=True)
+    prob = np.array(["." if v < 0 else io.vcfstr(float(v)) for v in values], dtype=object)[inverse.reshape(n, S)]
+    ad = format_allele_counts(allele_depths, allele_keep).astype(object)
+    strings = gt + ":" + prob + ":" + ad
+    return np.concatenate([np.full((n, 1), "GT:GPM:AD", dtype=object), strings], axis=1)
+
+
+def format_records(contigs, positions, depth, flags, admf, gt_index=None, gpm=None, ploidy=None):
     """VCF record lines of the rows the filter kept: contigs / positions (0-based) per row, depth int [n, S, 4], flags [n],
-    admf [n, 4] by allele index."""
+    admf [n, 4] by allele index.  With gt_index / gpm [n, S] (genotypes_device's, of these rows) and ploidy (one value or one per
+    sample) the sample columns are GT:GPM:AD instead of GT:AD with a null GT."""
     n = len(positions)
     if n == 0:
         return []
@@ -406,7 +485,12 @@ def format_records(contigs, positions, depth, flags, admf):
     f = np.take_along_axis(np.asarray(admf, dtype=np.float64), order, axis=1).round(3)
     ref, alts = order_as_vcf_alleles(order, keep)
     pop = d.sum(axis=1)
-    cols = format_samples_columns(d, keep)
+    if gt_index is None:
+        cols = format_samples_columns(d, keep)
+    else:
+        if gpm is None or ploidy is None:
+            raise ValueError("format_records: gt_index needs gpm and ploidy")
+        cols = format_genotype_columns(d, keep, gt_index, gpm, ploidy, refmasked)
     out = []
     for i in range(n):
         k = keep[i]
@@ -444,9 +528,12 @@ def block_rows_budget(n_samples):
     return device_unit_budget(16 * n_samples + 48, fraction=0.25, least=TILE, most=1 << 20)
 
 
-def find_snvs(targets, reference, source, maf=0.0, mad=0, ind_maf=0.1, ind_mad=3, min_ind=1, block_rows=None, tile=TILE, timings=None):
+def find_snvs(targets, reference, source, maf=0.0, mad=0, ind_maf=0.1, ind_mad=3, min_ind=1, block_rows=None, tile=TILE, timings=None,
+              genotypes=None):
     """Yield the VCF record lines of find-snvs: targets [(contig, start, stop)] (BED order; overlapping intervals are processed
-    again), reference an io.Reference, source an application.ReadSource with one file per sample."""
+    again), reference an io.Reference, source an application.ReadSource with one file per sample.  genotypes: None (GT:AD with a
+    null GT), or the settings of genotypes_device as a dict (ploidy, and optionally inbreeding, frequencies, error_rate; ploidy and
+    inbreeding one value, one per sample in the source's order, or a {sample: value} mapping): the records then carry GT:GPM:AD."""
     import torch
 
     lengths = dict(reference.contigs)
@@ -459,13 +546,27 @@ def find_snvs(targets, reference, source, maf=0.0, mad=0, ind_maf=0.1, ind_mad=3
             raise ValueError("target %s:%d-%d runs past the end of contig %s (length %d)" % (contig, start, stop, contig, lengths[contig]))
     files = _Files(source)
     S = len(files.samples)
+    if genotypes is not None:
+        genotypes = dict(genotypes)
+        for key in ("ploidy", "inbreeding"):
+            if isinstance(genotypes.get(key), dict):
+                genotypes[key] = [genotypes[key][s] for s in files.samples]
+        ploidy = genotypes["ploidy"]
     for block in plan_blocks(targets, int(block_rows or block_rows_budget(S))):
         depth, rows0 = _block_depths(files, block, tile=tile, timings=timings)
         ref = np.concatenate([bases_to_indices(reference.fetch(c, a, b).upper()) for c, a, b in block])
         ev = _events(timings)
         flags, admf = filter_device(depth, torch.from_numpy(ref), maf=maf, mad=mad, ind_maf=ind_maf, ind_mad=ind_mad, min_ind=min_ind)
+        if genotypes is not None:
+            eg = _events(timings)
+            gt, gpm = genotypes_device(depth, flags, admf, **genotypes)
+            if eg is not None:
+                eg[1].record()
+                timings["_events"].append(("genotypes", eg[0], eg[1]))
         idx = torch.nonzero(flags & 1).squeeze(1)
         kept_depth = depth.index_select(0, idx).cpu().numpy()
+        calls = {} if genotypes is None else dict(gt_index=gt.index_select(0, idx).cpu().numpy(), gpm=gpm.index_select(0, idx).cpu().numpy(),
+                                                  ploidy=ploidy)
         kept_flags, kept_admf, rows = flags.index_select(0, idx).cpu().numpy(), admf.index_select(0, idx).cpu().numpy(), idx.cpu().numpy()
         if ev is not None:
             ev[1].record()
@@ -473,7 +574,7 @@ def find_snvs(targets, reference, source, maf=0.0, mad=0, ind_maf=0.1, ind_mad=3
         t0 = time.perf_counter()
         w = np.searchsorted(rows0, rows, side="right") - 1
         positions = np.array([b[1] for b in block], dtype=np.int64)[w] + (rows - rows0[w])
-        lines = format_records([block[0][0]] * len(rows), positions, kept_depth, kept_flags, kept_admf)
+        lines = format_records([block[0][0]] * len(rows), positions, kept_depth, kept_flags, kept_admf, **calls)
         if timings is not None:
             timings["format"] = timings.get("format", 0.0) + time.perf_counter() - t0
             timings["records"] = timings.get("records", 0) + len(lines)

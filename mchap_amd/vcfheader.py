@@ -116,8 +116,9 @@ FIND_SNVS_FORMAT_FIELDS = [
 ]
 
 
-def find_snvs_header_lines(command, reference_path, samples, contigs, today=None, version=None):
-    """The header block of `find-snvs` as a list of lines: no FILTER lines, the reference FASTA named by its path as given."""
+def find_snvs_header_lines(command, reference_path, samples, contigs, today=None, version=None, genotypes=False):
+    """The header block of `find-snvs` as a list of lines: no FILTER lines, the reference FASTA named by its path as given.
+    genotypes: the records carry calls (GT:GPM:AD), so GPM is declared too, between GT and AD as in the FORMAT column."""
     from . import __version__
 
     d = today or date.today()
@@ -127,6 +128,9 @@ def find_snvs_header_lines(command, reference_path, samples, contigs, today=None
            "##reference=file:%s" % reference_path]
     out += ["##contig=<ID=%s,length=%d>" % (n, l) for n, l in contigs]
     out += ['##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % f for f in FIND_SNVS_INFO_FIELDS]
-    out += ['##FORMAT=<ID=%s,Number=%s,Type=%s,Description="%s">' % f for f in FIND_SNVS_FORMAT_FIELDS]
+    fmt = list(FIND_SNVS_FORMAT_FIELDS)
+    if genotypes:
+        fmt.insert(1, next(f for f in FORMAT_FIELDS if f[0] == "GPM"))
+    out += ['##FORMAT=<ID=%s,Number=%s,Type=%s,Description="%s">' % f for f in fmt]
     out.append("#" + "\t".join(["CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT"] + list(samples)))
     return out
