@@ -40,45 +40,29 @@
 
 typedef int (*init_fn)(const double *, const double *);
 typedef int (*simt_launch_fn)(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
-#define DECL_SPEC(k, g)                                                    \
-  extern "C" int mchap_spec_init_##k##_##g(const double *, const double *); \
-  extern "C" int mchap_spec_launch_##k##_##g(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
-#define DECL_SPECP(k, g)                                                    \
-  extern "C" int mchap_specp_init_##k##_##g(const double *, const double *); \
-  extern "C" int mchap_specp_launch_##k##_##g(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
-#define DECL_SIMT(k)                                                \
-  extern "C" int mchap_simt_init_##k(const double *, const double *); \
-  extern "C" int mchap_simt_launch_##k(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
-#define DECL_SPECS(k, g)                                                    \
-  extern "C" int mchap_specs_init_##k##_##g(const double *, const double *); \
-  extern "C" int mchap_specs_launch_##k##_##g(const mchap::SimtParams *, unsigned, size_t, hipStream_t); \
-  extern "C" int mchap_specd_init_##k##_##g(const double *, const double *); \
-  extern "C" int mchap_specd_launch_##k##_##g(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
+#define DECL_LAUNCH(p, l, s) extern "C" int mchap_##p##_##l##_##s(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
+#define DECL_OBJ(p, s) extern "C" int mchap_##p##_init_##s(const double *, const double *); DECL_LAUNCH(p, launch, s)
+#define DECL_SPEC(k, g) DECL_OBJ(spec, k##_##g)
+#define DECL_SPECP(k, g) DECL_OBJ(specp, k##_##g)
+// (the side-by-side and deep variants; and what only the instantiations with one chain per wavefront have: the launcher with
+// decision contexts per genotype of each phased variant, the speculative sampler's with a wavefront per replica of a ladder)
+#define DECL_SPECS(k, g) DECL_OBJ(specs, k##_##g) DECL_OBJ(specd, k##_##g) DECL_LAUNCH(spec, launchtw, k##_##g) \
+  DECL_LAUNCH(specp, launchc, k##_##g) DECL_LAUNCH(specs, launchc, k##_##g) DECL_LAUNCH(specd, launchc, k##_##g)
+#define DECL_SIMT(k) DECL_OBJ(simt, k)
 SPEC_LIST(DECL_SPEC)
 SPECP_LIST(DECL_SPECP)
 SPECS_LIST(DECL_SPECS)
 SIMT_LIST(DECL_SIMT)
-// the phased form's instantiations with decision contexts per genotype (one chain per wavefront; plain / side by side / deep)
-#define DECL_SPECC(k)                                                                                        \
-  extern "C" int mchap_specp_launchc_##k##_64(const mchap::SimtParams *, unsigned, size_t, hipStream_t); \
-  extern "C" int mchap_specs_launchc_##k##_64(const mchap::SimtParams *, unsigned, size_t, hipStream_t); \
-  extern "C" int mchap_specd_launchc_##k##_64(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
-DECL_SPECC(2) DECL_SPECC(3) DECL_SPECC(4) DECL_SPECC(5) DECL_SPECC(6) DECL_SPECC(7) DECL_SPECC(8)
 // ... and its instantiation with 128-bit haplotype words (simt_inst.hip -DSIMT_WIDE): the general fallback for wide targets
-extern "C" int mchap_simt_init_w(const double *, const double *);
-extern "C" int mchap_simt_launch_w(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
+DECL_OBJ(simt, w)
 extern "C" int mchap_coast_launch(const mchap::SimtParams *, unsigned, int, hipStream_t);
 // table completion of the phased sampler, one workgroup per chain and one wavefront per request (denovo_fillw_kernel.hpp): shipped
 #define FILLW_LIST(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#define DECL_FILLW(k)                                                    \
-  extern "C" int mchap_fillw_init_##k(const double *, const double *); \
-  extern "C" int mchap_fillw_launch_##k(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
+#define DECL_FILLW(k) DECL_OBJ(fillw, k)
 FILLW_LIST(DECL_FILLW)
 #ifdef MCHAP_TEST_KERNELS
 #define FILL_LIST(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#define DECL_FILL(k)                                                \
-  extern "C" int mchap_fill_init_##k(const double *, const double *); \
-  extern "C" int mchap_fill_launch_##k(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
+#define DECL_FILL(k) DECL_OBJ(fill, k)
 FILL_LIST(DECL_FILL)
 #define DECL_V1(r)                                                \
   extern "C" int mchap_v1_init_##r(const double *, const double *); \
@@ -152,31 +136,30 @@ struct SamplerTimer {
   }
 };
 
+// The instantiations of the speculative sampler (kernel 3) and of the phased form's three variants (kernel 5), one table
+enum Variant { VAR_SPEC, VAR_PHASED, VAR_SBS, VAR_DEEP };
+const char *const VARIANT_NAME[] = {"speculative sampler", "phased sampler", "phased sampler (side by side)", "phased sampler (deep)"};
 struct SpecInst {
-  int K, G;
+  int variant, K, G;
   init_fn init;
   simt_launch_fn launch;
+  simt_launch_fn launch_c;   // with decision contexts per genotype (phased, one chain per wavefront), else null
+  simt_launch_fn launch_tw;  // a wavefront per replica of a temperature ladder (speculative, one chain per wavefront), else null
 };
-#define ROW_SPEC(k, g) {k, g, mchap_spec_init_##k##_##g, mchap_spec_launch_##k##_##g},
-#define ROW_SPECP(k, g) {k, g, mchap_specp_init_##k##_##g, mchap_specp_launch_##k##_##g},
-const SpecInst SPEC_INSTS[] = {SPEC_LIST(ROW_SPEC)};
-const SpecInst SPECP_INSTS[] = {SPECP_LIST(ROW_SPECP)};
-#define ROW_SPECS(k, g) {k, g, mchap_specs_init_##k##_##g, mchap_specs_launch_##k##_##g},
-const SpecInst SPECS_INSTS[] = {SPECS_LIST(ROW_SPECS)};
-#define ROW_SPECD(k, g) {k, g, mchap_specd_init_##k##_##g, mchap_specd_launch_##k##_##g},
-const SpecInst SPECD_INSTS[] = {SPECS_LIST(ROW_SPECD)};
-const SpecInst *find_inst(const SpecInst *tab, size_t n, int K, int G) {
-  for (size_t i = 0; i < n; i++)
-    if (tab[i].K == K && tab[i].G == G) return &tab[i];
+#define LAUNCH_16(p, l, k) nullptr
+#define LAUNCH_32(p, l, k) nullptr
+#define LAUNCH_64(p, l, k) mchap_##p##_##l##_##k##_64
+#define ROW(v, p, k, g, c, tw) {v, k, g, mchap_##p##_init_##k##_##g, mchap_##p##_launch_##k##_##g, c, tw},
+#define ROW_SPEC(k, g) ROW(VAR_SPEC, spec, k, g, nullptr, LAUNCH_##g(spec, launchtw, k))
+#define ROW_SPECP(k, g) ROW(VAR_PHASED, specp, k, g, LAUNCH_##g(specp, launchc, k), nullptr)
+#define ROW_SPECS(k, g) ROW(VAR_SBS, specs, k, g, LAUNCH_##g(specs, launchc, k), nullptr)
+#define ROW_SPECD(k, g) ROW(VAR_DEEP, specd, k, g, LAUNCH_##g(specd, launchc, k), nullptr)
+const SpecInst SPEC_INSTS[] = {SPEC_LIST(ROW_SPEC) SPECP_LIST(ROW_SPECP) SPECS_LIST(ROW_SPECS) SPECS_LIST(ROW_SPECD)};
+const SpecInst *find_inst(int variant, int K, int G) {
+  for (const SpecInst &i : SPEC_INSTS)
+    if (i.variant == variant && i.K == K && i.G == G) return &i;
   return nullptr;
 }
-#define FIND_SPEC(K, G) find_inst(SPEC_INSTS, sizeof(SPEC_INSTS) / sizeof(SPEC_INSTS[0]), K, G)
-#define FIND_SPECP(K, G) find_inst(SPECP_INSTS, sizeof(SPECP_INSTS) / sizeof(SPECP_INSTS[0]), K, G)
-#define FIND_SPECS(K, G) find_inst(SPECS_INSTS, sizeof(SPECS_INSTS) / sizeof(SPECS_INSTS[0]), K, G)
-#define FIND_SPECD(K, G) find_inst(SPECD_INSTS, sizeof(SPECD_INSTS) / sizeof(SPECD_INSTS[0]), K, G)
-// ... and their launchers with decision contexts, by ploidy - 2: {plain, side by side, deep}
-#define ROW_SPECC(k) {mchap_specp_launchc_##k##_64, mchap_specs_launchc_##k##_64, mchap_specd_launchc_##k##_64},
-const simt_launch_fn SPECC_LAUNCH[7][3] = {ROW_SPECC(2) ROW_SPECC(3) ROW_SPECC(4) ROW_SPECC(5) ROW_SPECC(6) ROW_SPECC(7) ROW_SPECC(8)};
 
 }  // namespace
 
@@ -196,13 +179,7 @@ int mchap::ensure_init() {
   HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(mchap::c_ln), ln, sizeof(ln)));
   HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(mchap::c_ln_inv), ln_inv, sizeof(ln_inv)));
   for (const SpecInst &i : SPEC_INSTS)
-    if (i.init(ln, ln_inv) != 0) return fail(MCHAP_ERR_HIP, "constant tables of the speculative sampler <%d, %d>", i.K, i.G);
-  for (const SpecInst &i : SPECP_INSTS)
-    if (i.init(ln, ln_inv) != 0) return fail(MCHAP_ERR_HIP, "constant tables of the phased sampler <%d, %d>", i.K, i.G);
-  for (const SpecInst &i : SPECS_INSTS)
-    if (i.init(ln, ln_inv) != 0) return fail(MCHAP_ERR_HIP, "constant tables of the phased sampler <%d, %d> (side by side)", i.K, i.G);
-  for (const SpecInst &i : SPECD_INSTS)
-    if (i.init(ln, ln_inv) != 0) return fail(MCHAP_ERR_HIP, "constant tables of the phased sampler <%d, %d> (deep)", i.K, i.G);
+    if (i.init(ln, ln_inv) != 0) return fail(MCHAP_ERR_HIP, "constant tables of the %s <%d, %d>", VARIANT_NAME[i.variant], i.K, i.G);
   {
 #define ROW_SIMT_INIT(k) mchap_simt_init_##k,
 #define ROW_V1_INIT(r) mchap_v1_init_##r,
@@ -351,7 +328,7 @@ bool lane_supported(int K, int max_pos, int n_temps) {
 // step whose draws fit the staged window.
 int pipe_group(const Tune &T, int K) {
   if (K < 2 || K > 8) return 0;
-  if (T.pipe_group != 64 && FIND_SPECP(K, T.pipe_group)) return T.pipe_group;
+  if (T.pipe_group != 64 && find_inst(VAR_PHASED, K, T.pipe_group)) return T.pipe_group;
   return 64;
 }
 bool pipe_supported(const mchap_denovo_cfg *cfg, const Tune &T, int K, int max_pos) {
@@ -447,6 +424,23 @@ struct SimtCarve {
 };
 constexpr int PIPE_MAX_ROUNDS = 6;  // resume rounds of the phased sampler (counters in the workspace)
 
+// What a batch runs on and how its workspace is cut: decided in resolve() below and nowhere else -- the entry points read it here.
+struct Resolved {
+  Tune T;
+  BatchDims B;
+  Plan pl;
+  int rpad = 0;
+  size_t bt_bytes = 0;  // the break table at the head of the workspace: the layout's offsets count from behind it
+  size_t n_chains = 0;
+  // likelihood-cache tables: one per chain (a temperature ladder on the speculative sampler: one per REPLICA -- they run side by
+  // side, one wavefront each)
+  size_t n_caches = 0;
+  int packed_bits = 0;  // width of a packed genotype
+  bool keyed = false;   // ... of more than 63 bits: its words beside the (hashed) tags, so that a cache hit is always exact
+  int cache_slots = 0;
+  SimtCarve cv;
+};
+
 // Entries per chain of the likelihood cache.  The reference's cache is unbounded (assemble/mcmc.py: a dictionary per chain); a
 // chain that never settles -- phase-ambiguous samples of real pileups: docs/example locus015 requests ~100 likelihoods per step
 // and 95 % of them are genotypes it has seen -- re-evaluates what a small table has dropped: at 1024 entries three quarters of
@@ -461,16 +455,14 @@ size_t budget_on_device(size_t cap, size_t frac) {
   if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b / frac < cap) return free_b / frac;
   return cap;
 }
-int cache_slots_of(const mchap_denovo_cfg *cfg, const Tune &T, const Plan &pl, int n_units, const BatchDims &B) {
+int cache_slots_of(const mchap_denovo_cfg *cfg, const Resolved &R) {
   if (!cfg->llk_cache) return 0;
-  if (!T.cache_auto) return T.cache_slots;
-  const size_t ncc = (size_t)n_units * cfg->chains * (size_t)(pl.kind == SAMPLER_SPEC ? cfg->n_temps : 1);
-  const bool keyed = B.max_ploidy * mchap::allele_bits(B.max_allele) * B.max_pos > 63;
-  const size_t entry = 16 + (keyed ? (size_t)B.max_ploidy * (pl.wide ? 2 : 1) * 8 : 0);
+  if (!R.T.cache_auto || !use_simt(cfg)) return R.T.cache_slots;  // (kernel 1: 1024 unless named)
+  const size_t entry = 16 + (R.keyed ? (size_t)R.B.max_ploidy * (R.pl.wide ? 2 : 1) * 8 : 0);
   const size_t budget = budget_on_device(CACHE_BUDGET, 8);
   int slots = 1024;
-  while (slots > 32 && ncc * (size_t)slots * entry > budget) slots >>= 1;  // (a nearly full device: below the usual floor)
-  while (slots < 65536 && ncc * (size_t)(2 * slots) * entry <= budget) slots *= 2;
+  while (slots > 32 && R.n_caches * (size_t)slots * entry > budget) slots >>= 1;  // (a nearly full device: below the usual floor)
+  while (slots < 65536 && R.n_caches * (size_t)(2 * slots) * entry <= budget) slots *= 2;
   return slots;
 }
 
@@ -478,30 +470,30 @@ int cache_slots_of(const mchap_denovo_cfg *cfg, const Tune &T, const Plan &pl, i
 // device's free memory) over the batch's chains allow, at most 64; fewer than 8 are not worth the look-ups.  The piece sits at the
 // end of the workspace and a fit takes as many slots as the workspace it was handed holds.
 constexpr size_t CTX_BUDGET = (size_t)6 << 30;
-bool ctx_shape(const Plan &pl, const BatchDims &B, const Tune &T) {
-  return pl.kind == SAMPLER_PIPE && pl.G == 64 && !(T.flags & 524288) && B.max_ploidy * B.max_pos <= 192;
+bool ctx_shape(const Resolved &R) {
+  return R.pl.kind == SAMPLER_PIPE && R.pl.G == 64 && !(R.T.flags & 524288) && R.B.max_ploidy * R.B.max_pos <= 192;
 }
-size_t ctx_slot_bytes(const Plan &pl, const BatchDims &B) { return (size_t)mchap::spec_ctx_words(pl.K, B.max_pos) * 8; }
-int ctx_slots_for(size_t bytes, size_t n_chains, size_t slot_bytes) {
-  const size_t n = bytes / (n_chains * slot_bytes);
+size_t ctx_slot_bytes(const Resolved &R) { return (size_t)mchap::spec_ctx_words(R.pl.K, R.B.max_pos) * 8; }
+int ctx_slots_for(size_t bytes, const Resolved &R) {
+  const size_t n = bytes / (R.n_chains * ctx_slot_bytes(R));
   return n >= (size_t)mchap::SPEC_CTX_MAX ? mchap::SPEC_CTX_MAX : (n < 8 ? 0 : (int)n);
 }
-int ctx_slots_of(const mchap_denovo_cfg *cfg, const Tune &T, const Plan &pl, int n_units, const BatchDims &B) {
-  if (!ctx_shape(pl, B, T)) return 0;
-  return ctx_slots_for(budget_on_device(CTX_BUDGET, 8), (size_t)n_units * cfg->chains, ctx_slot_bytes(pl, B));
-}
 
-SimtCarve simt_carve(const mchap_denovo_cfg *cfg, const Plan &pl, int n_units, const BatchDims &B, int rpad, int cache_slots, int ctx_n = 0) {
+SimtCarve carve(const mchap_denovo_cfg *cfg, int n_units, const Resolved &R, int cache_slots, int ctx_n) {
+  const BatchDims &B = R.B;
+  const Plan &pl = R.pl;
+  const int rpad = R.rpad;
+  const size_t nc = R.n_chains;
   SimtCarve c;
+  if (!use_simt(cfg)) {  // kernel 1: the cache tables are its only piece, and it is not rounded
+    c.total = R.n_caches * cache_slots * 16;
+    return c;
+  }
   size_t o = 0;
-  const size_t nc = (size_t)n_units * cfg->chains;
-  // (a temperature ladder on the speculative sampler: a likelihood cache per REPLICA -- they run side by side, one wavefront each)
-  const size_t ncc = nc * (size_t)(pl.kind == SAMPLER_SPEC ? cfg->n_temps : 1);
-  c.cache = o; o += up256(ncc * cache_slots * 16);
-  // genotypes of more than 63 bits: their words beside the (hashed) tags, so that a cache hit is always exact
-  if (cache_slots > 0 && B.max_ploidy * mchap::allele_bits(B.max_allele) * B.max_pos > 63) {
+  c.cache = o; o += up256(R.n_caches * cache_slots * 16);
+  if (cache_slots > 0 && R.keyed) {
     c.key_words = B.max_ploidy * (pl.wide ? 2 : 1);  // (uint64 words per entry: K haplotype words of 64 or 128 bits)
-    c.ckeys = o; o += up256(ncc * cache_slots * c.key_words * 8);
+    c.ckeys = o; o += up256(R.n_caches * cache_slots * c.key_words * 8);
   }
   c.rt = o; o += up256((size_t)n_units * B.max_ma * rpad * 8);
   c.cntw = o; o += up256((size_t)n_units * rpad * 8);
@@ -518,7 +510,7 @@ SimtCarve simt_carve(const mchap_denovo_cfg *cfg, const Plan &pl, int n_units, c
   // deep units (more than four chunks of 64 reads): the haplotype products of every chain's current genotype for the
   // chunks beyond the fourth (denovo_spec_kernel.hpp BaseProductsG), [chain][ploidy][rpad] doubles
   if ((pl.kind == SAMPLER_PIPE || pl.kind == SAMPLER_SPEC) && rpad > 4 * 64) {
-    c.gbp = o; o += up256(nc * (size_t)(pl.kind == SAMPLER_SPEC ? cfg->n_temps : 1) * B.max_ploidy * rpad * 8);  // (a set per replica)
+    c.gbp = o; o += up256(R.n_caches * B.max_ploidy * rpad * 8);  // (a set per replica, as the caches)
     c.has_gbp = true;
   }
   if (pl.kind == SAMPLER_PIPE) {  // hand-over records of the phased sampler
@@ -528,10 +520,62 @@ SimtCarve simt_carve(const mchap_denovo_cfg *cfg, const Plan &pl, int n_units, c
     c.pipe_counts = o; o += up256((PIPE_MAX_ROUNDS + 2) * 4);
     c.ctx = o;
     c.ctx_n = ctx_n;
-    o += up256(nc * (size_t)ctx_n * ctx_slot_bytes(pl, B));
+    o += up256(nc * (size_t)ctx_n * ctx_slot_bytes(R));
   }
   c.total = o;
   return c;
+}
+
+// PLAN_ONLY: the sampler and the batch's dimensions, nothing asked of the device.  SIZING: the layout a caller should allocate for
+// (mchap_denovo_workspace_bytes) -- cache and context slots by their budgets.  FIT: the layout of a workspace of workspace_bytes
+// as handed over -- behind the break table the cache slots are halved until the pieces without contexts fit (below the floor: no
+// cache), and the contexts take the slots the bytes left over hold (cv.total then stands for the pieces before them).  Whoever
+// reads a fit's workspace resolves it the same way.
+enum ResolveMode { PLAN_ONLY, SIZING, FIT };
+int resolve(const mchap_denovo_cfg *cfg, int n_units, const mchap_unit *units_host, ResolveMode mode, int64_t workspace_bytes, Resolved &R) {
+  R.T = tune_of(cfg);
+  R.bt_bytes = break_table_bytes(cfg);
+  if (units_host) {
+    int rc = batch_dims(cfg, n_units, units_host, R.B);
+    if (rc) return rc;
+    rc = plan_sampler(cfg, R.T, R.B, R.pl);
+    if (rc) return rc;
+  } else if (use_simt(cfg)) {
+    return MCHAP_ERR_BAD_ARG;  // (only kernel 1's one piece is sized without the units)
+  }
+  R.rpad = 64 * R.pl.rpl;
+  R.n_chains = (size_t)n_units * cfg->chains;
+  R.n_caches = R.n_chains * (size_t)(R.pl.kind == SAMPLER_SPEC ? cfg->n_temps : 1);
+  R.packed_bits = R.B.max_ploidy * mchap::allele_bits(R.B.max_allele) * R.B.max_pos;
+  R.keyed = R.packed_bits > 63;
+  if (mode == PLAN_ONLY) return MCHAP_OK;
+  const int want_slots = cache_slots_of(cfg, R);
+  if (mode == SIZING) {
+    R.cache_slots = want_slots;
+    R.cv = carve(cfg, n_units, R, want_slots, ctx_shape(R) ? ctx_slots_for(budget_on_device(CTX_BUDGET, 8), R) : 0);
+    return MCHAP_OK;
+  }
+  if (workspace_bytes < (int64_t)R.bt_bytes)
+    return fail(MCHAP_ERR_BAD_ARG, "workspace of %lld bytes is too small (mchap_denovo_workspace_bytes)", (long long)workspace_bytes);
+  workspace_bytes -= (int64_t)R.bt_bytes;
+  const int floor = use_simt(cfg) ? 32 : 16;
+  int slots = want_slots;
+  R.cv = carve(cfg, n_units, R, slots, 0);
+  while (slots >= floor && (int64_t)R.cv.total > workspace_bytes) {
+    slots >>= 1;
+    R.cv = carve(cfg, n_units, R, slots, 0);
+  }
+  if (slots < floor && want_slots) {
+    slots = 0;
+    R.cv = carve(cfg, n_units, R, 0, 0);
+  }
+  if ((int64_t)R.cv.total > workspace_bytes)  // (never kernel 1: without a cache it has no piece)
+    return fail(MCHAP_ERR_BAD_ARG, "workspace of %lld bytes is too small: kernel %d needs at least %zu (mchap_denovo_workspace_bytes)",
+                (long long)workspace_bytes, cfg->kernel, R.cv.total);
+  R.cache_slots = slots;
+  if (ctx_shape(R) && workspace_bytes > (int64_t)R.cv.total)
+    R.cv.ctx_n = ctx_slots_for((size_t)(workspace_bytes - (int64_t)R.cv.total), R);
+  return MCHAP_OK;
 }
 
 template <int RPL>
@@ -562,11 +606,8 @@ int bp_cache_fits(const Tune &T, int G, size_t lds, int K) {
   return ((lds + 15) & ~(size_t)15) + mchap::spec_bp_cache_bytes(K) <= 160 * 1024 ? 1 : 0;
 }
 
-#define DECL_SPEC_TW(k) extern "C" int mchap_spec_launchtw_##k##_64(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
-DECL_SPEC_TW(2) DECL_SPEC_TW(3) DECL_SPEC_TW(4) DECL_SPEC_TW(5) DECL_SPEC_TW(6) DECL_SPEC_TW(7) DECL_SPEC_TW(8)
-
 int launch_spec(const Tune &T, int K, int G, const mchap::SimtParams &P, int n_units, int chains, int n_temps, void *timer, hipStream_t stream) {
-  const SpecInst *inst = FIND_SPEC(K, G);
+  const SpecInst *inst = find_inst(VAR_SPEC, K, G);
   if (!inst) return fail(MCHAP_ERR_LIMIT, "speculative sampler: no instantiation for ploidy %d with %d lanes per chain", K, G);
   size_t lds = mchap::spec_lds_bytes(K, P.max_pos, P.max_allele, n_temps, G);
   if (lds > 160 * 1024) return fail(MCHAP_ERR_LIMIT, "speculative sampler needs %zu bytes of LDS", lds);
@@ -576,15 +617,13 @@ int launch_spec(const Tune &T, int K, int G, const mchap::SimtParams &P, int n_u
   const long long n_chains = (long long)n_units * chains;
   // A temperature ladder with one chain per wavefront: a workgroup of n_temps wavefronts per chain, one replica each
   // (denovo_spec_kernel<.., TW>; tuning flag 16384: the replicas one after the other on one wavefront, as before round 4)
-  if (G == 64 && n_temps > 1 && n_temps <= mchap::SPEC_TW_MAX && !(T.flags & 16384) && K >= 2 && K <= 8) {
+  if (inst->launch_tw && n_temps > 1 && n_temps <= mchap::SPEC_TW_MAX && !(T.flags & 16384)) {
     const size_t per_wave = (lds + 63) & ~(size_t)63;
     const size_t lds_tw = mchap::spec_tw_exchange_bytes(K, n_temps) + per_wave * n_temps;
     if (lds_tw <= 160 * 1024) {
-      const simt_launch_fn tw[] = {mchap_spec_launchtw_2_64, mchap_spec_launchtw_3_64, mchap_spec_launchtw_4_64, mchap_spec_launchtw_5_64,
-                                   mchap_spec_launchtw_6_64, mchap_spec_launchtw_7_64, mchap_spec_launchtw_8_64};
       Q.tw_lds = (int)per_wave;
       SamplerTimer tm(timer, stream);
-      const int e = tw[K - 2](&Q, (unsigned)n_chains, lds_tw, stream);
+      const int e = inst->launch_tw(&Q, (unsigned)n_chains, lds_tw, stream);
       if (e != 0) return fail(MCHAP_ERR_HIP, "launch of denovo_spec_kernel<%d, 64, replicas side by side>: %s", K, hipGetErrorString((hipError_t)e));
       return MCHAP_OK;
     }
@@ -648,14 +687,13 @@ int launch_lane(const Tune &T, int K, const mchap::SimtParams &P, int n_units, i
 // The phased sampler (kernel 5): denovo_spec_kernel<K, G, true> for the first steps, denovo_coast_kernel for the
 // chains' long no-move stretches, denovo_spec_kernel again for the chains handed back.
 int launch_pipe(const Tune &T, int K, int G, mchap::SimtParams P, int n_units, int chains, int32_t *lists, int32_t *counts, void *timer,
-                hipStream_t stream, bool shallow_units, int max_reads) {
+                hipStream_t stream, bool shallow_units, int max_reads, int packed_bits) {
   // deep units (product rows in the workspace) or more than 128 (haplotype, position) pairs: the "deep" instantiation; else a
   // batch with a unit of at most 64 reads: the one that evaluates such a unit's requests side by side; else the plain one
   const SpecInst *inst = nullptr;
-  int variant = 0;  // 0 plain, 1 side by side, 2 deep
-  if (G == 64 && (P.gbp != nullptr || (K * P.max_pos > 128 && !(T.flags & 512)))) inst = FIND_SPECD(K, G), variant = 2;
-  else if (shallow_units && G == 64 && !(T.flags & 256)) inst = FIND_SPECS(K, G), variant = 1;
-  if (!inst) inst = FIND_SPECP(K, G), variant = 0;
+  if (G == 64 && (P.gbp != nullptr || (K * P.max_pos > 128 && !(T.flags & 512)))) inst = find_inst(VAR_DEEP, K, G);
+  else if (shallow_units && G == 64 && !(T.flags & 256)) inst = find_inst(VAR_SBS, K, G);
+  if (!inst) inst = find_inst(VAR_PHASED, K, G);
   if (!inst) return fail(MCHAP_ERR_LIMIT, "phased sampler: no instantiation for ploidy %d with %d lanes per chain", K, G);
   simt_launch_fn launch = inst->launch;
   size_t lds = mchap::spec_lds_bytes(K, P.max_pos, P.max_allele, 1, G);
@@ -667,7 +705,7 @@ int launch_pipe(const Tune &T, int K, int G, mchap::SimtParams P, int n_units, i
   // Tuning flag 8192: never (the table in the workspace is probed, as before round 4: same traces).
   auto per_cu = [](size_t b) { const size_t w = (160 * 1024) / b; return w > 8 ? (size_t)8 : w; };
   const size_t lds_nolc = lds;
-  const bool lc_shape = P.bp_cache && P.d.cache_slots > 0 && !(T.flags & 8192) && K * mchap::allele_bits(P.max_allele) * P.max_pos <= 63;
+  const bool lc_shape = P.bp_cache && P.d.cache_slots > 0 && !(T.flags & 8192) && packed_bits <= 63;
   if (lc_shape) {
     const size_t with = ((lds + 15) & ~(size_t)15) + mchap::spec_lc_bytes();
     if (with <= 160 * 1024 && per_cu(with) >= per_cu(lds)) {
@@ -683,7 +721,7 @@ int launch_pipe(const Tune &T, int K, int G, mchap::SimtParams P, int n_units, i
   int bp_cache_c = P.bp_cache;
   uint64_t *ctx_region = nullptr;
   int ctx_n = 0;
-  if (G == 64 && P.ctx != nullptr && P.ctx_n > 0 && K >= 2 && K <= 8) {
+  if (inst->launch_c && P.ctx != nullptr && P.ctx_n > 0) {
     // the front cache beside the contexts: whole, halved or not at all -- the largest that keeps the launch's wavefronts per CU
     // (the contexts answer most of what the front cache did); if nothing does, as in the other launches
     const size_t cx = mchap::spec_ctx_lds_bytes(K, P.max_pos);
@@ -703,7 +741,7 @@ int launch_pipe(const Tune &T, int K, int G, mchap::SimtParams P, int n_units, i
       }
     }
     if (with <= 160 * 1024) {
-      launch_c = SPECC_LAUNCH[K - 2][variant];
+      launch_c = inst->launch_c;
       lds_c = with;
       ctx_region = P.ctx;
       ctx_n = P.ctx_n;
@@ -850,23 +888,18 @@ int mchap_denovo_sampler_name(const mchap_denovo_cfg *cfg, int n_units, const mc
   int rc = validate_cfg(cfg);
   if (rc) return rc;
   if (!out || out_len < 1 || !units_host || n_units < 1) return fail(MCHAP_ERR_BAD_ARG, "NULL buffer");
-  BatchDims B;
-  rc = batch_dims(cfg, n_units, units_host, B);
+  Resolved R;
+  rc = resolve(cfg, n_units, units_host, PLAN_ONLY, 0, R);
   if (rc) return rc;
-  Plan pl;
-  rc = plan_sampler(cfg, tune_of(cfg), B, pl);
-  if (rc) return rc;
-  plan_name(pl, out, (size_t)out_len);
+  plan_name(R.pl, out, (size_t)out_len);
   return MCHAP_OK;
 }
 
 int mchap_denovo_trace_words_per_haplotype(const mchap_denovo_cfg *cfg, int n_units, const mchap_unit *units_host) {
   if (validate_cfg(cfg) || !units_host || n_units < 1) return -1;
-  BatchDims B;
-  if (batch_dims(cfg, n_units, units_host, B)) return -1;
-  Plan pl;
-  if (plan_sampler(cfg, tune_of(cfg), B, pl)) return -1;
-  return pl.wide ? 2 : 1;
+  Resolved R;
+  if (resolve(cfg, n_units, units_host, PLAN_ONLY, 0, R)) return -1;
+  return R.pl.wide ? 2 : 1;
 }
 
 #if defined(MCHAP_STATS) || defined(MCHAP_PHASES)
@@ -916,34 +949,19 @@ int mchap_debug_lane_stats(unsigned long long *out, int reset) {
 #endif
 
 #ifdef MCHAP_TEST_KERNELS
-/* test library only (tools/pipe_records.py, tests): the phased sampler's hand-over records and round counters as the
- * last fit on this workspace left them.  records: [n_units * chains] PipeState (128 bytes each), counts: [8] int32. */
-int mchap_debug_pipe_records(const mchap_denovo_cfg *cfg, int n_units, const mchap_unit *units_host, const void *workspace,
-                             void *records, int32_t *counts) {
-  BatchDims B;
-  if (batch_dims(cfg, n_units, units_host, B)) return MCHAP_ERR_BAD_ARG;
-  const Tune T = tune_of(cfg);
-  Plan pl;
-  if (plan_sampler(cfg, T, B, pl) || pl.kind != SAMPLER_PIPE) return fail(MCHAP_ERR_BAD_ARG, "not a phased-sampler batch");
-  const SimtCarve cv = simt_carve(cfg, pl, n_units, B, 64 * pl.rpl, cache_slots_of(cfg, T, pl, n_units, B));
-  const unsigned char *ws = reinterpret_cast<const unsigned char *>(workspace) + break_table_bytes(cfg);
+/* test library only (tests): the chains' interval tables as the last fit on this workspace -- of workspace_bytes, as that fit was
+ * handed it -- left them: [n_units * chains][2][max_pos (max_pos + 1) / 2] float64 (NaN: not evaluated, -1: the step has no
+ * options, else the total move probability).  workspace_bytes is the LAST argument: a caller of the earlier five-argument form
+ * then leaves a size undefined, which can only fail the call or select a layout inside the sized workspace -- never a pointer. */
+int mchap_debug_pipe_memo(const mchap_denovo_cfg *cfg, int n_units, const mchap_unit *units_host, const void *workspace, double *memo,
+                          int64_t workspace_bytes) {
+  Resolved R;
+  int rc = resolve(cfg, n_units, units_host, FIT, workspace_bytes, R);
+  if (rc) return rc;
+  if (R.pl.kind != SAMPLER_PIPE) return fail(MCHAP_ERR_BAD_ARG, "not a phased-sampler batch");
+  const unsigned char *ws = reinterpret_cast<const unsigned char *>(workspace) + R.bt_bytes;
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(records, ws + cv.pipe_state, (size_t)n_units * cfg->chains * sizeof(mchap::PipeState), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(counts, ws + cv.pipe_counts, (PIPE_MAX_ROUNDS + 2) * 4, hipMemcpyDeviceToHost));
-  return MCHAP_OK;
-}
-/* ... and the chains' interval tables [n_units * chains][2][max_pos (max_pos + 1) / 2] float64 (NaN: not evaluated,
- * -1: the step has no options, else the total move probability) */
-int mchap_debug_pipe_memo(const mchap_denovo_cfg *cfg, int n_units, const mchap_unit *units_host, const void *workspace, double *memo) {
-  BatchDims B;
-  if (batch_dims(cfg, n_units, units_host, B)) return MCHAP_ERR_BAD_ARG;
-  const Tune T = tune_of(cfg);
-  Plan pl;
-  if (plan_sampler(cfg, T, B, pl) || pl.kind != SAMPLER_PIPE) return fail(MCHAP_ERR_BAD_ARG, "not a phased-sampler batch");
-  const SimtCarve cv = simt_carve(cfg, pl, n_units, B, 64 * pl.rpl, cache_slots_of(cfg, T, pl, n_units, B));
-  const unsigned char *ws = reinterpret_cast<const unsigned char *>(workspace) + break_table_bytes(cfg);
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(memo, ws + cv.pipe_memo, (size_t)n_units * cfg->chains * 2 * mchap::spec_memo_entries(B.max_pos) * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(memo, ws + R.cv.pipe_memo, R.n_chains * 2 * mchap::spec_memo_entries(R.B.max_pos) * 8, hipMemcpyDeviceToHost));
   return MCHAP_OK;
 }
 #endif
@@ -964,15 +982,10 @@ int64_t mchap_denovo_lds_bytes(int n_reads, int n_pos, int max_allele, int ploid
 
 int64_t mchap_denovo_workspace_bytes(const mchap_denovo_cfg *cfg, int n_units, const mchap_unit *units_host) {
   if (!cfg || n_units <= 0) return 0;
-  const Tune T = tune_of(cfg);
-  const int64_t bt = (int64_t)break_table_bytes(cfg);
-  if (!use_simt(cfg)) return bt + (int64_t)n_units * cfg->chains * (cfg->llk_cache ? T.cache_slots : 0) * 16;
-  if (!units_host) return -1;
-  BatchDims B;
-  if (batch_dims(cfg, n_units, units_host, B)) return -1;
-  Plan pl;
-  if (plan_sampler(cfg, T, B, pl)) return -1;
-  return bt + (int64_t)simt_carve(cfg, pl, n_units, B, 64 * pl.rpl, cache_slots_of(cfg, T, pl, n_units, B), ctx_slots_of(cfg, T, pl, n_units, B)).total;
+  Resolved R;
+  // (kernel 1's one piece does not depend on the units: they may be NULL, and are not looked at)
+  if (resolve(cfg, n_units, use_simt(cfg) ? units_host : nullptr, SIZING, 0, R)) return -1;
+  return (int64_t)(R.bt_bytes + R.cv.total);
 }
 
 static int fit_batch_device_impl(const mchap_denovo_cfg *cfg, int n_units, const mchap_unit *units_dev,
@@ -1019,15 +1032,15 @@ static int fit_batch_device_impl(const mchap_denovo_cfg *cfg, int n_units, const
   rc = ensure_init();
   if (rc) return rc;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-  BatchDims B;
-  rc = batch_dims(cfg, n_units, units_host, B);
+  Resolved R;
+  rc = resolve(cfg, n_units, units_host, FIT, workspace ? workspace_bytes : 0, R);
   if (rc) return rc;
-  const Tune T = tune_of(cfg);
-  Plan pl;
-  rc = plan_sampler(cfg, T, B, pl);
-  if (rc) return rc;
+  const Tune &T = R.T;
+  const BatchDims &B = R.B;
+  const Plan &pl = R.pl;
+  const SimtCarve &cv = R.cv;
   const int rpl = pl.rpl;
-  const int rpad = 64 * rpl;
+  const int rpad = R.rpad;
 
   mchap::SimtParams SP;
   std::memset(&SP, 0, sizeof(SP));
@@ -1060,45 +1073,23 @@ static int fit_batch_device_impl(const mchap_denovo_cfg *cfg, int n_units, const
   {
     // head of the caller's workspace: this call's break table, copied on this call's stream
     const size_t n = (size_t)(P.max_pos + 1) * P.max_pos;
-    const size_t bt_bytes = break_table_bytes(cfg);
-    if (!workspace || workspace_bytes < (int64_t)bt_bytes)
-      return fail(MCHAP_ERR_BAD_ARG, "workspace of %lld bytes is too small (mchap_denovo_workspace_bytes)", (long long)workspace_bytes);
     double *bt_dev = reinterpret_cast<double *>(workspace);
     if (cfg->break_table)
       HIP_TRY(hipMemcpyAsync(bt_dev, cfg->break_table, n * sizeof(double), hipMemcpyHostToDevice, stream));
     else
       HIP_TRY(hipMemsetAsync(bt_dev, 0, n * sizeof(double), stream));
     P.break_table = bt_dev;
-    workspace = reinterpret_cast<unsigned char *>(workspace) + bt_bytes;
-    workspace_bytes -= (int64_t)bt_bytes;
   }
+  unsigned char *ws = reinterpret_cast<unsigned char *>(workspace) + R.bt_bytes;
   HIP_TRY(hipMemsetAsync(status, 0, sizeof(int32_t) * n_units, stream));
   P.cache = nullptr;
   P.cache_slots = 0;
 
   if (use_simt(cfg)) {
-    const int want_slots = cache_slots_of(cfg, T, pl, n_units, B);
-    int slots = want_slots;
-    SimtCarve cv = simt_carve(cfg, pl, n_units, B, rpad, slots);
-    while (slots >= 32 && (int64_t)cv.total > workspace_bytes) {
-      slots >>= 1;
-      cv = simt_carve(cfg, pl, n_units, B, rpad, slots);
-    }
-    if (slots < 32 && want_slots) {
-      slots = 0;
-      cv = simt_carve(cfg, pl, n_units, B, rpad, 0);
-    }
-    if (!workspace || (int64_t)cv.total > workspace_bytes)
-      return fail(MCHAP_ERR_BAD_ARG, "workspace of %lld bytes is too small: kernel %d needs at least %zu (mchap_denovo_workspace_bytes)",
-                  (long long)workspace_bytes, cfg->kernel, cv.total);
-    unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
-    // decision contexts: as many slots per chain as the rest of the workspace holds (mchap_denovo_workspace_bytes sized it by its budget)
-    if (ctx_shape(pl, B, T) && workspace_bytes > (int64_t)cv.total) {
-      const int cn = ctx_slots_for((size_t)(workspace_bytes - (int64_t)cv.total), (size_t)n_units * cfg->chains, ctx_slot_bytes(pl, B));
-      if (cn > 0) {
-        SP.ctx = reinterpret_cast<uint64_t *>(ws + cv.ctx);
-        SP.ctx_n = cn;
-      }
+    const int slots = R.cache_slots;
+    if (cv.ctx_n > 0) {  // decision contexts: the slots per chain that the rest of the workspace holds
+      SP.ctx = reinterpret_cast<uint64_t *>(ws + cv.ctx);
+      SP.ctx_n = cv.ctx_n;
     }
     if (slots > 0) {
       P.cache = reinterpret_cast<uint64_t *>(ws + cv.cache);
@@ -1107,8 +1098,7 @@ static int fit_batch_device_impl(const mchap_denovo_cfg *cfg, int n_units, const
       // Narrow genotypes on the speculative / phased sampler: tagged with this call's epoch, nothing cleared (tuning flag 65536:
       // clear as before; flag 64, the parity suite's lane-per-request completion, forms its own tags)
       uint64_t epoch = 0;
-      if ((pl.kind == SAMPLER_PIPE || pl.kind == SAMPLER_SPEC) && !(T.flags & (64 | 65536)) &&
-          B.max_ploidy * mchap::allele_bits(B.max_allele) * B.max_pos <= 32) {
+      if ((pl.kind == SAMPLER_PIPE || pl.kind == SAMPLER_SPEC) && !(T.flags & (64 | 65536)) && R.packed_bits <= 32) {
         // the caller's number (a property of the call: the Python host draws from one sequence for every library copy in the
         // process -- two copies counting on their own could tag different data alike), else this copy's counter
         epoch = cfg->cache_epoch > 0 ? (uint64_t)cfg->cache_epoch : g_cache_epoch.fetch_add(1) + 1;
@@ -1116,7 +1106,7 @@ static int fit_batch_device_impl(const mchap_denovo_cfg *cfg, int n_units, const
       }
       SP.cache_epoch = epoch << 33;
       if (!epoch)
-        HIP_TRY(hipMemsetAsync(ws + cv.cache, 0, (size_t)n_units * cfg->chains * (pl.kind == SAMPLER_SPEC ? cfg->n_temps : 1) * slots * 16, stream));
+        HIP_TRY(hipMemsetAsync(ws + cv.cache, 0, R.n_caches * slots * 16, stream));
       if (cv.key_words) {
         P.cache_keys = reinterpret_cast<uint64_t *>(ws + cv.ckeys);
         P.cache_key_words = cv.key_words;
@@ -1183,7 +1173,7 @@ static int fit_batch_device_impl(const mchap_denovo_cfg *cfg, int n_units, const
 #endif
       case SAMPLER_PIPE:
         return launch_pipe(T, pl.K, pl.G, SP, n_units, cfg->chains, reinterpret_cast<int32_t *>(ws + cv.pipe_lists),
-                           reinterpret_cast<int32_t *>(ws + cv.pipe_counts), cfg->timer, stream, B.min_reads <= 64, B.max_reads);
+                           reinterpret_cast<int32_t *>(ws + cv.pipe_counts), cfg->timer, stream, B.min_reads <= 64, B.max_reads, R.packed_bits);
       case SAMPLER_SPEC: return launch_spec(T, pl.K, pl.G, SP, n_units, cfg->chains, cfg->n_temps, cfg->timer, stream);
       default: return launch_simt(pl.K, SP, n_units, cfg->chains, lds_simt, cfg->timer, stream, pl.wide);  // lanes over chains
     }
@@ -1201,15 +1191,10 @@ static int fit_batch_device_impl(const mchap_denovo_cfg *cfg, int n_units, const
   }
   if (lds > 160 * 1024)
     return fail(MCHAP_ERR_LIMIT, "a unit needs %zu bytes of LDS (> 160 KiB): dense float64 staging does not fit", lds);
-  if (cfg->llk_cache && workspace && workspace_bytes > 0) {
-    const int64_t rows = (int64_t)n_units * cfg->chains;
-    int slots = T.cache_slots;
-    while (slots >= 16 && rows * slots * 16 > workspace_bytes) slots >>= 1;
-    if (slots >= 16) {
-      P.cache = reinterpret_cast<uint64_t *>(workspace);
-      P.cache_slots = slots;
-      HIP_TRY(hipMemsetAsync(workspace, 0, (size_t)(rows * slots * 16), stream));
-    }
+  if (R.cache_slots > 0) {
+    P.cache = reinterpret_cast<uint64_t *>(ws);
+    P.cache_slots = R.cache_slots;
+    HIP_TRY(hipMemsetAsync(ws, 0, cv.total, stream));
   }
   return launch_denovo(rpl, P, n_units, cfg->chains, lds, cfg->timer, stream);
 #else

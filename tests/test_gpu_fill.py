@@ -40,7 +40,7 @@ def _tables(reads, flags, **kw):
         memo = np.zeros((U * model.chains, 2, E), dtype=np.float64)
         f = _lib.lib().mchap_debug_pipe_memo
         f.restype = C.c_int
-        rc = f(C.byref(b.cfg), U, _lib.ptr(b.units_host), C.c_void_p(b.d_ws.data_ptr()), _lib.ptr(memo))
+        rc = f(C.byref(b.cfg), U, _lib.ptr(b.units_host), C.c_void_p(b.d_ws.data_ptr()), _lib.ptr(memo), C.c_int64(b.ws_bytes))
         assert rc == 0, _lib.last_error()
         return memo
     finally:

@@ -15,8 +15,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _tables(reads, flags, **kw):
-    """First phase of the phased sampler (steps, table completion, first coasting launch) -> the chains' interval tables."""
+def _first_phase(reads, flags, halve_workspace=False, **kw):
+    """First phase of the phased sampler (steps, table completion, first coasting launch) -> the chains' interval tables, read
+    back where a fit with that workspace put them (mchap_debug_pipe_memo), and the batch."""
     import torch
 
     from mchap_amd import DenovoMCMC, _lib
@@ -29,6 +30,8 @@ def _tables(reads, flags, **kw):
         model = DenovoMCMC(random_seed=42, kernel=5, **kw)
         b = DenovoDeviceBatch(model, reads)
         assert "phased" in b.sampler_name
+        if halve_workspace:
+            b.ws_bytes //= 2
         b.run()
         torch.cuda.synchronize()
         U, M = reads.shape[0], reads.shape[2]
@@ -36,12 +39,16 @@ def _tables(reads, flags, **kw):
         memo = np.zeros((U * model.chains, 2, E), dtype=np.float64)
         f = _lib.lib().mchap_debug_pipe_memo
         f.restype = C.c_int
-        rc = f(C.byref(b.cfg), U, _lib.ptr(b.units_host), C.c_void_p(b.d_ws.data_ptr()), _lib.ptr(memo))
+        rc = f(C.byref(b.cfg), U, _lib.ptr(b.units_host), C.c_void_p(b.d_ws.data_ptr()), _lib.ptr(memo), C.c_int64(b.ws_bytes))
         assert rc == 0, _lib.last_error()
-        return memo
+        return memo, b
     finally:
         for k in ("MCHAP_HIP_TEST_KERNELS", "MCHAP_HIP_PIPE_STOP", "MCHAP_HIP_FLAGS"):
             os.environ.pop(k, None)
+
+
+def _tables(reads, flags, **kw):
+    return _first_phase(reads, flags, **kw)[0]
 
 
 CASES = {
@@ -87,6 +94,23 @@ def test_tables_equal_the_in_kernel_completion(case):
     for flags in (2048, 4096, 2048 | 4096, 32768, 32768 | 2048):
         alt = _tables(reads, flags, **kw)
         assert np.array_equal(np.isnan(alt), np.isnan(old)) and np.array_equal(alt[done].view(np.uint64), old[done].view(np.uint64)), flags
+
+
+def test_the_reader_follows_the_fit_into_a_smaller_workspace():
+    """A fit handed half the bytes mchap_denovo_workspace_bytes asked for halves its likelihood caches and takes the decision
+    contexts the rest holds: the pieces behind the caches -- the interval tables among them -- move.  The reader resolves the layout
+    as the fit did, so it finds the same tables (and the traces do not depend on either size)."""
+    from mchap_amd.synth import synth_units
+
+    reads, _, _ = synth_units(16, ploidy=4, n_pos=8, n_reads=200, first_unit=11)
+    kw = dict(ploidy=4, n_alleles=[2] * 8, steps=60, chains=2)
+    memo, whole = _first_phase(reads, 0, **kw)
+    memo_half, half = _first_phase(reads, 0, halve_workspace=True, **kw)
+    assert half.ws_bytes == whole.ws_bytes // 2
+    assert (~np.isnan(memo)).any(axis=(1, 2)).mean() > 0.5
+    assert np.array_equal(memo, memo_half, equal_nan=True)
+    for x, y in zip(whole.traces(), half.traces()):
+        assert np.array_equal(np.asarray(x).view(np.uint8), np.asarray(y).view(np.uint8))
 
 
 def _run(reads, flags, **kw):
