@@ -1,4 +1,4 @@
-"""The host side of `mchap assemble` over a BLOCK of target loci at once: what application.ReadSource.reads / encode_reads
+"""The host side of `mchap assemble` over a BLOCK of target loci at once: what sources.ReadSource.reads / encode_reads
 do locus by locus (reference application/baseclass.py:140-210: extract_read_variants, allele calls, de-duplicated rows with
 counts, depths) as array operations over every (locus x read x SNV) cell of the block, ragged -- loci differ in their numbers
 of SNVs and reads.  The per-locus functions stay the definition: tests/test_blockpath.py holds the two against each other
@@ -142,7 +142,7 @@ def extract_block(loci, cols, sample, min_quality=20, skip_duplicates=True, skip
 
 
 def pile_from_matrices(loci, matrices, tables=None):
-    """A BlockPileup from character / quality matrices the caller has already (application.MatrixSource): matrices[l] =
+    """A BlockPileup from character / quality matrices the caller has already (sources.MatrixSource): matrices[l] =
     (chars [rows, M] as str or uint8 ASCII codes, quals [rows, M]) of locus l."""
     L = len(loci)
     M, snv_start, _ = tables if tables is not None else locus_tables(loci)
@@ -180,7 +180,7 @@ class BlockEncoding:
                  "ucell_of_row")
 
     def per_locus(self, l):
-        """dict(chars, calls, depth, ucalls, counts) of locus l, shaped like application.encode_reads's."""
+        """dict(chars, calls, depth, ucalls, counts) of locus l, shaped like sources.encode_reads's."""
         p = self.pile
         chars, _ = p.matrices(l)
         m = int(p.M[l])

@@ -309,7 +309,7 @@ class CompactCallReads:
     where the float64 [U, n_reads, M, max_allele] tensor does: `shape`, `len`, indexing and numpy conversion give that tensor
     (formed on the host by blockpath.expand_call_units when someone asks for it: a stand-in sampler of the tests, the host classes
     on downloaded traces), `counts` the [U, n_reads] counts in the same way, and on_device() both as device tensors formed there
-    from the int8 calls -- what CallingMCMC.start_batch_summaries and application._run_exact_groups use."""
+    from the int8 calls -- what application._group_inputs hands to CallingMCMC.start_batch_summaries and, through _run_exact_groups, to ExactDeviceBatch."""
 
     ndim, dtype = 4, np.dtype(np.float64)
 

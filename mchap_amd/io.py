@@ -206,7 +206,7 @@ class Locus:
 
     def __init__(self, rec, frequency_tag=None, allele_filter=None):
         self.contig, self.start, self.stop = rec["chrom"], rec["pos"] - 1, rec["pos"] - 1 + len(rec["ref"])
-        self.name = rec.get("id", ".")   # (what application.MatrixSource keys a record's pileup matrices by)
+        self.name = rec.get("id", ".")   # (what sources.MatrixSource keys a record's pileup matrices by)
         sequences = (rec["ref"],) + rec["alts"]
         n = len(sequences)
         self.mask_reference_allele = "REFMASKED" in rec["info"]

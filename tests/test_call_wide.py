@@ -111,6 +111,56 @@ def test_call_program_with_a_stubbed_sampler(tmp_path, monkeypatch, capsys):
     assert [ln for ln in both if ln.split("\t")[2] != "BEYOND"] == wide
 
 
+def test_call_writes_the_samplers_mci_into_its_records(tmp_path, monkeypatch):
+    """MCI of `mchap call` is a sampler statistic: per sample in FORMAT field 10, the number of samples above 0 in INFO between NS and DP.
+    Two samples of different ploidy (so the stub knows whose units it has), three records, one of them REFMASKED; the stub answers
+    mci = 1 for the tetraploid sample's units and 0 for the diploid's, and every other field equals a run where it answers 0 throughout."""
+    from mchap_amd import application
+    from mchap_amd.calling_mcmc import CallingMCMC, CallSummary
+
+    mci_of = {}
+
+    def stub(self, reads, read_counts=None, initial=None, haplotypes=None, prior=None, stream_ids=None, burn=0, incongruence_threshold=0.6,
+             max_states=512, stream=None):
+        U, H, K = len(reads), haplotypes.shape[1], int(self.ploidy)
+        n_obs = int(self.chains) * (int(self.steps) - burn)
+        return dict(done=[CallSummary(genotypes=np.full((1, K), H - 1, np.int32), counts=np.array([n_obs]), n_obs=n_obs,
+                                      alleles=np.full(K, H - 1, np.int32), gprob=1.0, sprob=1.0, mci=mci_of[K], n_allele=H) for _ in range(U)])
+
+    monkeypatch.setattr(CallingMCMC, "start_batch_summaries", stub)
+    monkeypatch.setattr(application, "_call_stream", lambda i: None)
+    vcf = str(tmp_path / "haps.vcf")
+    with open(os.path.join(HERE, "simple.output.deep.assemble.vcf")) as fh:
+        lines = [ln.rstrip("\n") for ln in fh]
+    head = [ln for ln in lines if ln.startswith("#")]
+    recs = [ln.split("\t") for ln in lines if not ln.startswith("#") and ln.split("\t")[4] != "."]   # (the two records with SNVs)
+    masked = list(recs[1])
+    masked[1], masked[2], masked[7] = str(int(masked[1]) + 1), "MASKED", masked[7].replace(";NS=", ";REFMASKED;NS=")
+    with open(vcf, "w") as fh:
+        fh.write("\n".join(head + ["\t".join(f) for f in recs + [masked]]) + "\n")
+    bams = {"SAMPLE1": os.path.join(HERE, DEEP[0]), "SAMPLE2": os.path.join(HERE, DEEP[1])}
+
+    def run():
+        return [ln.split("\t") for ln in application.call(vcf, dict(bams), ploidy={"SAMPLE1": 4, "SAMPLE2": 2}, steps=300, burn=100, seed=5)]
+
+    mci_of.update({4: 1, 2: 0})
+    got = run()
+    mci_of.update({4: 0, 2: 0})
+    quiet = run()
+    assert len(got) == len(quiet) == 3 and "REFMASKED" in got[2][7].split(";") and all(f[6] == "PASS" for f in got)
+    for f, q in zip(got, quiet):
+        s1, s2 = f[9].split(":"), f[10].split(":")
+        assert len(s1) == len(s2) == 11 and s1[10] == "1" and s2[10] == "0"
+        info = f[7].split(";")
+        at = info.index("MCI=1")
+        assert info[at - 1].startswith("NS=") and info[at + 1].startswith("DP=")
+        # everything else as without incongruence
+        assert q[9].split(":")[10] == q[10].split(":")[10] == "0" and "MCI=0" in q[7].split(";")
+        assert s1[:10] == q[9].split(":")[:10] and s2[:10] == q[10].split(":")[:10]
+        assert [x for x in info if x != "MCI=1"] == [x for x in q[7].split(";") if x != "MCI=0"]
+        assert f[:7] + f[8:9] == q[:7] + q[8:9]
+
+
 # ---- the oracle beyond 256 known haplotypes, against the reference ----
 def _wide_case(z, i):
     p = "c%d_" % i
