@@ -411,6 +411,17 @@ int mchap_call_reads_from_calls_device(int n_units, const int8_t *calls, const i
                                        int n_reads, int n_pos, int max_allele, double p_call, double p_other, double *reads,
                                        int64_t *read_counts, void *stream);
 
+/* The same tensors with base qualities in use (--use-base-phred-scores): quals (int16, laid out like calls) holds every cell's
+ * summed base quality, p_call / p_other two float64 tables of n_qual >= 1 entries the host computes as encoding.as_probabilistic
+ * does: p_call[q] = prob_of_qual(q) * (1 - error_rate), p_other[q] = (1 - p_call[q]) / 3.  Cell (u, r, j, a) with r < unit_rows[u]
+ * and call >= 0 is p_call[q] if a == call, else p_other[q], q the cell's quality (clamped into [0, n_qual): the host checks the
+ * qualities of called cells before the upload; the quality of a gap cell is not read); everything else -- gaps, alleles a position
+ * does not have, padding rows, counts, the environment variable -- as above.  The device does no arithmetic on the probabilities. */
+int mchap_call_reads_from_calls_quals_device(int n_units, const int8_t *calls, const int16_t *quals, const int64_t *counts,
+                                             const int64_t *unit_rows, const int64_t *unit_call_off, const int64_t *unit_count_off,
+                                             const int8_t *n_alleles, int n_reads, int n_pos, int max_allele, const double *p_call,
+                                             const double *p_other, int n_qual, double *reads, int64_t *read_counts, void *stream);
+
 /* Measurement (bench.py): a timer is a pair of HIP events owned by the caller.  A fit whose cfg.timer is set records them on
  * its own stream right around its sampler launches; mchap_timer_ms waits for the second event and returns the span in
  * milliseconds (< 0: nothing recorded).  No process-wide state: fits on different threads / streams use different timers. */

@@ -209,6 +209,8 @@ def lib():
         L.mchap_snv_genotypes_device.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int] + [C.c_void_p] * 2 + [C.c_int] + [C.c_double] * 2 + \
             [C.c_void_p] * 3
         L.mchap_call_reads_from_calls_device.argtypes = [C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_double] * 2 + [C.c_void_p] * 3
+        L.mchap_call_reads_from_calls_quals_device.argtypes = [C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_int] + \
+            [C.c_void_p] * 3
         L.mchap_timer_ms.argtypes = [C.c_void_p]
         L.mchap_timer_destroy.argtypes = [C.c_void_p]
         _libs[path] = L
@@ -284,6 +286,7 @@ EXPORTS = [
     "mchap_call_mcmc_batch_device",
     "mchap_call_mcmc_batch",
     "mchap_call_reads_from_calls_device",
+    "mchap_call_reads_from_calls_quals_device",
     "mchap_version",
     "mchap_last_error",
     "mchap_device_count",

@@ -47,25 +47,38 @@ def device_unit_budget(bytes_per_unit, fraction=0.5, least=1, most=1 << 20, rese
 
 class _BlockReads:
     """unit["reads"][sample] of a record on the block path: what ReadSource.reads returns (calls, depth, counts, the distinct
-    rows as `ucalls`) as views into the block's encoding; the float `dists` are formed from `ucalls` on first use -- --report GL,
-    the oracle replay -- and never for a unit whose tensor the device forms."""
+    rows as `ucalls`, with their qualities `uquals` where base qualities are in use) as views into the block's encoding; the float
+    `dists` are formed from them on first use -- --report GL, the oracle replay -- and never for a unit whose tensor the device
+    forms.  qtable: the block's quality table (None: base qualities ignored)."""
 
-    __slots__ = ("d", "n_alleles", "error_rate")
+    __slots__ = ("d", "n_alleles", "error_rate", "qtable")
 
-    def __init__(self, d, n_alleles, error_rate):
-        self.d, self.n_alleles, self.error_rate = d, n_alleles, error_rate
+    def __init__(self, d, n_alleles, error_rate, qtable=None):
+        self.d, self.n_alleles, self.error_rate, self.qtable = d, n_alleles, error_rate, qtable
 
     def __getitem__(self, key):
         if key == "dists" and "dists" not in self.d:
-            self.d["dists"] = encoding.encode_read_distributions(self.n_alleles, self.d["ucalls"], None, error_rate=self.error_rate)
+            self.d["dists"] = _block_dists(self.n_alleles, self.d["ucalls"], self.d.get("uquals"), self.error_rate, self.qtable)
         return self.d[key]
+
+
+def _block_dists(n_alleles, ucalls, uquals, error_rate, qtable):
+    """The float rows of a unit's distinct rows on the block path: encoding.encode_read_distributions of the calls -- with base
+    qualities in use, every called cell's probability read from the block's quality table (what the device does with the same
+    calls and qualities)."""
+    if qtable is None or uquals is None:
+        return encoding.encode_read_distributions(n_alleles, ucalls, None, error_rate=error_rate)
+    if len(ucalls) == 0 or len(n_alleles) == 0:
+        return np.empty((len(ucalls), len(n_alleles), int(max(n_alleles)) if len(n_alleles) else 0), dtype=float)
+    probs = qtable[np.where(np.asarray(ucalls) >= 0, np.asarray(uquals, dtype=np.int64), 0)]
+    return encoding.as_probabilistic(ucalls, n_alleles, probs)
 
 
 def _exact_units(records, source, samples, prior_tag, allele_filter=None, block_path=False):
     """Everything `call-exact` needs from the input side, record by record: the locus, per sample the encoded reads,
     and which (record, sample) units need the kernel (a record with a single haplotype, or no variable position, has
     one genotype with probability 1; an invalid record is not called at all).
-    block_path: False = the reads of every (record, sample) through source.reads (the definition); None / True = extracted and
+    block_path: False = the reads of every (record, sample) through source.reads (the definition); None / True / "wide" = extracted and
     encoded for the whole block at once (mchap_amd/blockpath.py; the caller has checked _block_path_takes(source)) -- a block
     the array path does not take (BlockPathUnavailable) goes record by record."""
     loci = [Locus(rec, prior_tag, allele_filter) for rec in records]
@@ -76,7 +89,7 @@ def _exact_units(records, source, samples, prior_tag, allele_filter=None, block_
         try:
             blk = _block_encodings(loci, source, samples)
         except BlockPathUnavailable:
-            pass   # (an unsorted file, a row-hash collision: this block goes record by record, under True as well)
+            pass   # (an unsorted file, a row-hash collision, a negative quality: this block goes record by record, under True as well)
     out = []
     for li, (rec, locus) in enumerate(zip(records, loci)):
         H, M = locus.haplotypes.shape
@@ -89,17 +102,18 @@ def _exact_units(records, source, samples, prior_tag, allele_filter=None, block_
             per = {s: source.reads(locus, s) for s in samples}
         elif M == 0:
             # (no variable position: nothing is sampled; the per-record encoder on the block's character matrix)
-            per = {s: encode_reads(locus, *blk["encs"][i].pile.matrices(li), source.error_rate, False) for s, i in blk["si"].items()}
+            per = {s: encode_reads(locus, *blk["encs"][i].pile.matrices(li), source.error_rate, source.use_phred) for s, i in blk["si"].items()}
         else:
-            per = {s: _BlockReads(blk["encs"][i].per_locus(li), locus.n_alleles, source.error_rate) for s, i in blk["si"].items()}
+            per = {s: _BlockReads(blk["encs"][i].per_locus(li), locus.n_alleles, source.error_rate, blk["qtable"]) for s, i in blk["si"].items()}
         out.append(dict(rec=rec, locus=locus, invalid=invalid, reads=per, needs_kernel=(invalid is None and M > 0 and H > 1),
                         block=blk, li=li))
     return out
 
 
 def _group_compact_reads(units, members, Rmax, A):
-    """The reads of a chunk of a shape group as int8 calls of the units' distinct rows (device.CompactCallReads: its on_device()
-    is one call of mchap_call_reads_from_calls_device); None when the units do not come from a block encoding (the caller then
+    """The reads of a chunk of a shape group as int8 calls of the units' distinct rows -- and their int16 qualities where base
+    qualities are in use -- (device.CompactCallReads: its on_device() is one call of mchap_call_reads_from_calls_device, or of
+    mchap_call_reads_from_calls_quals_device); None when the units do not come from a block encoding (the caller then
     fills and uploads the float tensor)."""
     blk = units[members[0][0]].get("block")
     if blk is None or any(units[ri].get("block") is not blk for ri in {ri for ri, _ in members}):
@@ -109,7 +123,8 @@ def _group_compact_reads(units, members, Rmax, A):
 
     li = np.fromiter((units[ri]["li"] for ri, _ in members), dtype=np.int64, count=len(members))
     si = np.fromiter((blk["si"][s] for _, s in members), dtype=np.int64, count=len(members))
-    return CompactCallReads(*bp.call_unit_inputs(blk["encs"], li, si, blk["nal"]), Rmax, A, error_rate=blk["error_rate"])
+    compact = bp.call_unit_inputs(blk["encs"], li, si, blk["nal"])
+    return CompactCallReads(*compact[:6], Rmax, A, error_rate=blk["error_rate"], quals=compact[6] if len(compact) > 6 else None)
 
 
 def _max_allele(sr, locus):
@@ -279,6 +294,12 @@ CALL_BLOCK_PATH_DEFAULT = False
 
 def _call_block_path(block_path, source):
     """The block_path keyword of call / call_exact as _exact_units takes it: False when the source needs the per-record path."""
+    if isinstance(block_path, str):
+        if block_path != "wide":
+            raise ValueError("block_path: None, True, False or 'wide'")
+        if not _block_path_takes(source, wide=True):
+            raise ValueError("block_path='wide': the inputs need the per-record path")
+        return block_path
     if block_path is False or (block_path is None and not CALL_BLOCK_PATH_DEFAULT):
         return False
     if not _block_path_takes(source):
@@ -339,7 +360,10 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
     alignment files read whole, one file per sample, base qualities ignored -- or the call fails (a single block the array
     path refuses -- an unsorted file, a row-hash collision -- goes record by record instead); False = always record by
     record (the definition: tests hold the two against each other line for line); None = the block path where the inputs allow
-    it and CALL_BLOCK_PATH_DEFAULT is set, else record by record.  A `calling` backend is evaluated unit by unit either way."""
+    it and CALL_BLOCK_PATH_DEFAULT is set, else record by record; "wide" = the block path for a wider set of inputs -- base
+    qualities in use (int8 calls and int16 qualities are uploaded, rows are de-duplicated as their float rows are) and pooled
+    samples (a pool's reads: those of its files, concatenated), the files still BAM files read whole, else the call fails -- opt-in
+    until its rate has been measured against the per-record path.  A `calling` backend is evaluated unit by unit either way."""
     from .vcfheader import report_fields
 
     source = _source(sample_bams, base_error_rate, use_base_phred_scores, read_kw)
@@ -462,7 +486,9 @@ def assemble(bed_path, variants_vcf_path, reference_sequences, sample_bams, ploi
     posterior haplotypes and the record fields) as array operations over the whole block (mchap_amd/blockpath.py, _BlockState
     below) whenever the inputs allow -- alignment files read whole, one file per sample, base qualities ignored --, else locus
     by locus; False = always locus by locus (the definition: tests hold the two against each other line for line); True =
-    fail if the block path cannot take the inputs."""
+    fail if the block path cannot take the inputs; "wide" = the block path with base qualities in use and with pooled samples
+    too (int16 qualities go to the device with the int8 calls), failing for inputs even that does not take -- files fetched region
+    by region, a custom sampler."""
     from .assemble import DenovoMCMC
     from .classes import PosteriorGenotypeDistribution
     from .device import DenovoRaggedBatch, PassesInFlight
@@ -514,9 +540,13 @@ def assemble(bed_path, variants_vcf_path, reference_sequences, sample_bams, ploi
         import torch
 
         streams = [torch.cuda.Stream(), torch.cuda.Stream()]
-    fast = block_path is not False and sampler is None and _block_path_takes(source)
+    if isinstance(block_path, str) and block_path != "wide":
+        raise ValueError("block_path: None, True, False or 'wide'")
+    fast = block_path is not False and sampler is None and _block_path_takes(source, wide=block_path == "wide")
     if block_path is True and not fast:
         raise ValueError("block_path=True: the inputs need the per-locus path")
+    if block_path == "wide" and not fast:
+        raise ValueError("block_path='wide': the inputs need the per-locus path")
     run = SimpleNamespace(source=source, samples=samples, ploidy_of=ploidy_of, inbreeding_of=inbreeding_of, temps_of=temps_of,
                           by_contig=by_contig, fetch=fetch, seq_known=seq_known, timings=timings, steps=steps, chains=chains, seed=seed,
                           burn=burn, incongruence_threshold=incongruence_threshold, mcmc_kw=mcmc_kw, report=report,
@@ -536,8 +566,9 @@ def assemble(bed_path, variants_vcf_path, reference_sequences, sample_bams, ploi
 # on the block's stream and not waited for), finish() stage 2 (the block's results on the host -- it waits for its own launches
 # only --, its records formatted and yielded).  `run`: the settings of the run, built once in assemble(). ----
 def _start_block(block, stream, run):
-    """Stage 1 of a block on the path the run takes: the array path (run.block_path None / True), locus by locus for a block it
-    does not take (an unsorted file, a row-hash collision) unless the caller insisted, or locus by locus throughout (False)."""
+    """Stage 1 of a block on the path the run takes: the array path (run.block_path None / True / "wide"), locus by locus for a block it
+    does not take (an unsorted file, a row-hash collision, a negative quality) unless the caller insisted with True, or locus by locus
+    throughout (False)."""
     if run.block_path is not False:
         from .blockpath import BlockPathUnavailable
 
@@ -727,7 +758,7 @@ class _BlockState:
         self.lx = lx = [l for li, l in enumerate(loci) if li not in self.skipped]
         self.xi_of = {li: xi for xi, li in enumerate(li for li in range(len(loci)) if li not in self.skipped)}
         blk = _block_encodings(lx, run.source, samples, timings=timings, inflate_together=True)
-        self.enc, self.nal = blk["encs"], blk["nal"]
+        self.enc, self.nal, self.qtable = blk["encs"], blk["nal"], blk["qtable"]
         self.M, self.snv_start, _ = blk["tables"]
         M = self.M
         # the sampler's units: every (sample, locus with SNVs), one launch per (ploidy, temperature ladder, wide) present
@@ -778,10 +809,11 @@ class _BlockState:
                  n_pos=np.tile(self.M[use], len(sis)), max_allele=np.tile(self.amax[use], len(sis)),
                  nalleles_off=np.tile(self.snv_start[use], len(sis)), ploidy=np.full(m * len(sis), K, dtype=np.int64),
                  bits=np.tile(self.bits[use], len(sis)))
+        with_quals = dict(quals=np.concatenate([p[5] for p in parts])) if len(parts[0]) > 5 else {}   # (base qualities in use)
         F = np.array([np.nan if run.inbreeding_of(run.samples[si]) is None else float(run.inbreeding_of(run.samples[si])) for si in sis])
         batch = self.factory(_model(run, K, temps), u["calls"], u["reads_off"], u["n_reads"], u["n_pos"], u["max_allele"], u["ploidy"],
                              u["counts"], u["counts_off"], self.nal, u["nalleles_off"], inbreeding=np.repeat(F, m),
-                             error_rate=run.source.error_rate)
+                             error_rate=run.source.error_rate, **with_quals)
         for k, si in enumerate(sis):
             self.unit_at[si, use, 0] = bi
             self.unit_at[si, use, 1] = k * m + np.arange(m)
@@ -940,7 +972,7 @@ class _BlockState:
             d = self.enc[si].per_locus(xi)
             sr = dict(calls=d["calls"], depth=d["depth"], counts=d["counts"])
             if "GL" in run.report and M:
-                sr["dists"] = encoding.encode_read_distributions(locus.n_alleles, d["ucalls"], None, error_rate=run.source.error_rate)
+                sr["dists"] = _block_dists(locus.n_alleles, d["ucalls"], d["uquals"], run.source.error_rate, self.qtable)
             encoded[sample] = sr
             if M == 0:
                 res = _no_snv_result(int(run.ploidy_of(sample)))

@@ -169,6 +169,52 @@ def pile_from_matrices(loci, matrices, tables=None):
     return out
 
 
+def concat_piles(piles):
+    """The pile of a pool of samples: the piles of its (read group, file) pairs -- all over the same loci -- concatenated row-wise,
+    locus by locus, in the order given (what sources.ReadSource.reads concatenates per locus)."""
+    piles = list(piles)
+    if len(piles) == 1:
+        return piles[0]
+    first = piles[0]
+    L, M = first.L, first.M
+    out = BlockPileup()
+    out.L, out.M, out.snv_start = L, M, first.snv_start
+    rows_of = [(p.row_start[1:] - p.row_start[:-1]).astype(np.int64) for p in piles]
+    total = np.sum(rows_of, axis=0).astype(np.int64) if L else np.zeros(0, dtype=np.int64)
+    out.row_start = np.zeros(L + 1, dtype=np.int64)
+    np.cumsum(total, out=out.row_start[1:])
+    out.cell_start = np.zeros(L + 1, dtype=np.int64)
+    np.cumsum(total * M, out=out.cell_start[1:])
+    out.row_locus = np.repeat(np.arange(L, dtype=np.int64), total)
+    out.cell_of_row = out.cell_start[out.row_locus] + (np.arange(int(out.row_start[-1]), dtype=np.int64) - out.row_start[out.row_locus]) * M[out.row_locus]
+    out.chars = np.empty(int(out.cell_start[-1]), dtype=np.uint8)
+    out.quals = np.empty(int(out.cell_start[-1]), dtype=np.int16)
+    before = np.zeros(L, dtype=np.int64)   # rows of the locus that earlier piles have placed
+    for p, n in zip(piles, rows_of):
+        # (a pile's cells lie locus after locus: cell k of its locus l goes to the pool's locus l, behind the earlier piles' rows)
+        owner, k = _ragged_arange(n * M)
+        dest = (out.cell_start[:-1] + before * M)[owner] + k
+        out.chars[dest] = p.chars
+        out.quals[dest] = p.quals
+        before += n
+    return out
+
+
+def qual_prob_table(error_rate, n):
+    """float64 [n]: the probability a called cell of quality q gives its allele, prob_of_qual(q) * (1 - error_rate) -- entry q is
+    what encoding.encode_read_distributions computes for such a cell."""
+    from .encoding import prob_of_qual
+
+    return np.asarray(prob_of_qual(np.arange(max(int(n), 1))) * (1.0 - error_rate), dtype=np.float64)
+
+
+def canonical_qualities(quality_table):
+    """int64 [n]: for every quality the first quality with the same table value (the table saturates: from some quality on
+    1 - 10^(-q/10) rounds to the same float64, and rows that differ only there are the same float rows)."""
+    _, first, inv = np.unique(np.asarray(quality_table, dtype=np.float64), return_index=True, return_inverse=True)
+    return first[inv.reshape(-1)].astype(np.int64)
+
+
 _MULT = (np.random.default_rng(0x5eed).integers(1, 1 << 62, size=256, dtype=np.int64).astype(np.uint64) << np.uint64(1)) | np.uint64(1)
 
 
@@ -177,10 +223,11 @@ class BlockEncoding:
     order of first appearance with their counts."""
 
     __slots__ = ("pile", "calls", "depth", "rcount", "rcalls", "dp", "urow_start", "ucell_start", "ucalls", "ucounts", "urow_locus",
-                 "ucell_of_row")
+                 "ucell_of_row", "uquals")
 
     def per_locus(self, l):
-        """dict(chars, calls, depth, ucalls, counts) of locus l, shaped like sources.encode_reads's."""
+        """dict(chars, calls, depth, ucalls, counts, uquals) of locus l, shaped like sources.encode_reads's; uquals: the int16
+        qualities of the distinct rows (of each group's first row), None for an encoding without qualities."""
         p = self.pile
         chars, _ = p.matrices(l)
         m = int(p.M[l])
@@ -188,7 +235,8 @@ class BlockEncoding:
         ua, ub = int(self.ucell_start[l]), int(self.ucell_start[l + 1])
         nu = int(self.urow_start[l + 1] - self.urow_start[l])
         return dict(chars=chars, calls=self.calls[a:b].reshape(chars.shape), depth=self.depth[int(p.snv_start[l]):int(p.snv_start[l + 1])],
-                    ucalls=self.ucalls[ua:ub].reshape(nu, m), counts=self.ucounts[int(self.urow_start[l]):int(self.urow_start[l + 1])])
+                    ucalls=self.ucalls[ua:ub].reshape(nu, m), counts=self.ucounts[int(self.urow_start[l]):int(self.urow_start[l + 1])],
+                    uquals=None if self.uquals is None else self.uquals[ua:ub].reshape(nu, m))
 
 
 def allele_lut(loci, n_snv):
@@ -210,10 +258,14 @@ def allele_lut(loci, n_snv):
     return lut
 
 
-def encode_block(loci, pile, lut=None):
+def encode_block(loci, pile, lut=None, quality_table=None):
     """Allele index of every character (the first allele of the SNV that has it, else -1), depth per SNV (characters that are
     not '-'), reads and called cells per locus, DP (the rounded mean depth), distinct call rows with counts.  lut: allele_lut of
-    the loci (shared by the samples of a block)."""
+    the loci (shared by the samples of a block).
+    quality_table (base qualities in use: blockpath.qual_prob_table): rows are then distinct as their float rows are (the reference
+    de-duplicates on the bytes of the float tensor, application/baseclass.py:207) -- two rows are one iff cell by cell both are gaps
+    (whatever the qualities there) or have the same call and the same table value -- and `uquals` holds the qualities of each
+    group's first row.  A called cell with a negative quality, or one beyond the table: BlockPathUnavailable."""
     L, M = pile.L, pile.M
     n_snv = int(pile.snv_start[-1])
     enc = BlockEncoding()
@@ -235,9 +287,18 @@ def encode_block(loci, pile, lut=None):
         enc.dp = np.where(M > 0, np.round(sums / np.maximum(M, 1)), np.nan)
     # distinct rows per locus: rows sorted by (locus, a 64-bit hash of the row), equal neighbours grouped, every row then
     # compared cell by cell with the first row of its group (a hash collision would show there: none has been seen)
+    cq = None
+    if quality_table is not None:
+        called = calls >= 0
+        q = pile.quals.astype(np.int64)
+        if (called & ((q < 0) | (q >= len(quality_table)))).any():
+            raise BlockPathUnavailable("a called cell's base quality is negative or beyond the quality table")
+        # the canonical quality of a cell: the first quality with the same table value; 0 in a gap
+        cq = np.where(called, canonical_qualities(quality_table)[np.where(called, q, 0)], 0) if len(q) else q
     rows = np.flatnonzero(row_M > 0)  # (rows of loci without SNVs have no cells; such loci are not sampled)
     if len(rows):
-        h_cell = (calls.astype(np.int64) + 2).astype(np.uint64) * _MULT[jj % 256] + _MULT[(jj // 256) % 256] * (jj // 256).astype(np.uint64)
+        cell_key = calls.astype(np.int64) + 2 if cq is None else (calls.astype(np.int64) + 2) + (cq << 8)
+        h_cell = cell_key.astype(np.uint64) * _MULT[jj % 256] + _MULT[(jj // 256) % 256] * (jj // 256).astype(np.uint64)
         h = np.add.reduceat(h_cell, pile.cell_of_row[rows])
         o = np.lexsort((h, pile.row_locus[rows]))
         hs, ls = h[o], pile.row_locus[rows][o]
@@ -250,7 +311,10 @@ def encode_block(loci, pile, lut=None):
         counts = np.bincount(gid, minlength=len(rep)).astype(np.int64)
         rep_of_row = np.full(n_rows, -1, dtype=np.int64)
         rep_of_row[rows] = rep[gid]
-        same = calls == calls[pile.cell_of_row[rep_of_row[row_of_cell]] + jj]
+        rep_cell = pile.cell_of_row[rep_of_row[row_of_cell]] + jj
+        same = calls == calls[rep_cell]
+        if cq is not None:
+            same &= cq == cq[rep_cell]
         if not same.all():
             raise BlockPathUnavailable("row hash collision")
         order = np.argsort(rep, kind="stable")         # in order of first appearance, locus after locus
@@ -265,6 +329,9 @@ def encode_block(loci, pile, lut=None):
     np.cumsum(nu * M, out=enc.ucell_start[1:])
     ur, uj = _ragged_arange(M[enc.urow_locus])
     enc.ucalls = calls[pile.cell_of_row[urows][ur] + uj] if len(urows) else np.zeros(0, dtype=np.int8)
+    enc.uquals = None
+    if quality_table is not None:
+        enc.uquals = pile.quals[pile.cell_of_row[urows][ur] + uj] if len(urows) else np.zeros(0, dtype=np.int16)
     enc.ucell_of_row = enc.ucell_start[enc.urow_locus] + (np.arange(len(urows), dtype=np.int64) - enc.urow_start[enc.urow_locus]) * M[enc.urow_locus]
     enc.ucounts = ucounts
     return enc
@@ -273,7 +340,8 @@ def encode_block(loci, pile, lut=None):
 def unit_inputs(enc, use):
     """The sampler's compact input for the loci `use` (indices, each with at least one SNV) of one sample's encoding: int8 calls
     of the distinct rows, unit after unit, their counts, and per unit (rows, first call element, first count or -1).  A locus
-    without reads is one all-gap row without counts (assemble/mcmc.py:132-137)."""
+    without reads is one all-gap row without counts (assemble/mcmc.py:132-137).  An encoding with qualities adds a sixth array: the
+    int16 qualities, laid out like the calls (zeros in an all-gap row)."""
     M = enc.pile.M[use]
     nu = (enc.urow_start[1:] - enc.urow_start[:-1])[use]
     R = np.maximum(nu, 1)
@@ -286,6 +354,11 @@ def unit_inputs(enc, use):
     c_off = np.cumsum(nu) - nu
     owner, k = _ragged_arange(nu)
     counts = enc.ucounts[enc.urow_start[use][owner] + k]
+    if enc.uquals is not None:
+        quals = np.zeros(len(calls), dtype=np.int16)
+        owner, k = _ragged_arange(src_n)
+        quals[off[owner] + k] = enc.uquals[enc.ucell_start[use][owner] + k]
+        return calls, counts, R, off, np.where(nu > 0, c_off, -1), quals
     return calls, counts, R, off, np.where(nu > 0, c_off, -1)
 
 
@@ -295,7 +368,8 @@ def call_unit_inputs(encs, loci, samples, n_alleles):
     encodings --, all with the same number M >= 1 of SNVs.  n_alleles: int8, the alleles at every SNV of the block's loci,
     concatenated (the order of locus_tables' positions).  Returns (int8 calls of the units' distinct rows, unit after unit, their
     counts, rows per unit [U], first call element [U], first count [U], n_alleles int8 [U, M]).  A unit without reads has 0 rows
-    (not unit_inputs' all-gap row: the call programs pad a group with rows of weight 0)."""
+    (not unit_inputs' all-gap row: the call programs pad a group with rows of weight 0).  Encodings with qualities add a seventh
+    array: the int16 qualities of the rows, laid out like the calls (mchap_call_reads_from_calls_quals_device)."""
     loci, samples = np.asarray(loci, dtype=np.int64), np.asarray(samples, dtype=np.int64)
     U = len(loci)
     pile = encs[0].pile
@@ -317,19 +391,28 @@ def call_unit_inputs(encs, loci, samples, n_alleles):
     count_off = np.cumsum(nu) - nu
     calls = np.empty(int(cells.sum()), dtype=np.int8)
     counts = np.empty(int(nu.sum()), dtype=np.int64)
+    quals = np.empty(len(calls), dtype=np.int16) if U and encs[0].uquals is not None else None
     for s, idx in members:
         e = encs[s]
         owner, k = _ragged_arange(cells[idx])
         calls[call_off[idx][owner] + k] = e.ucalls[src_cell[idx][owner] + k]
+        if quals is not None:
+            quals[call_off[idx][owner] + k] = e.uquals[src_cell[idx][owner] + k]
         owner, k = _ragged_arange(nu[idx])
         counts[count_off[idx][owner] + k] = e.ucounts[src_row[idx][owner] + k]
     nal = np.asarray(n_alleles, dtype=np.int8)[pile.snv_start[loci][:, None] + np.arange(M, dtype=np.int64)[None, :]]
+    if quals is not None:
+        return calls, counts, nu, call_off, count_off, nal.reshape(U, M), quals
     return calls, counts, nu, call_off, count_off, nal.reshape(U, M)
 
 
-def expand_call_units(calls, counts, unit_rows, unit_call_off, unit_count_off, n_alleles, n_reads, max_allele, error_rate=0.0024):
+def expand_call_units(calls, counts, unit_rows, unit_call_off, unit_count_off, n_alleles, n_reads, max_allele, error_rate=0.0024,
+                      quals=None, quality_table=None):
     """What mchap_call_reads_from_calls_device writes, on the host (the rule of include/mchap_hip.h; the tests hold the kernel and
-    the programs' fill loop against it): (reads float64 [U, n_reads, M, max_allele], read_counts int64 [U, n_reads])."""
+    the programs' fill loop against it): (reads float64 [U, n_reads, M, max_allele], read_counts int64 [U, n_reads]).
+    quals (int16, laid out like calls): what mchap_call_reads_from_calls_quals_device writes -- a called cell of quality q gives
+    its allele quality_table[q] (default: blockpath.qual_prob_table of the error rate) and every other allele
+    (1 - quality_table[q]) / 3."""
     nal = np.asarray(n_alleles, dtype=np.int64)
     U, M = nal.shape
     R, A = int(n_reads), int(max_allele)
@@ -337,13 +420,24 @@ def expand_call_units(calls, counts, unit_rows, unit_call_off, unit_count_off, n
     p_call = 1.0 - error_rate
     p_other = (1.0 - p_call) / 3.0
     padded = np.full((U, R, M), -1, dtype=np.int64)
+    padded_q = np.zeros((U, R, M), dtype=np.int64)
     read_counts = np.zeros((U, R), dtype=np.int64)
     u, r = _ragged_arange(rows)
     if len(u):
         src = np.asarray(unit_call_off, dtype=np.int64)[u] + r * M
         padded[u, r] = np.asarray(calls)[src[:, None] + np.arange(M, dtype=np.int64)[None, :]]
+        if quals is not None:
+            padded_q[u, r] = np.asarray(quals)[src[:, None] + np.arange(M, dtype=np.int64)[None, :]]
         read_counts[u, r] = np.asarray(counts)[np.asarray(unit_count_off, dtype=np.int64)[u] + r]
     allele = np.arange(A, dtype=np.int64)
+    if quals is not None:
+        called = padded >= 0
+        qmax = int(padded_q[called].max(initial=0))
+        table = qual_prob_table(error_rate, qmax + 1) if quality_table is None else np.asarray(quality_table, dtype=np.float64)
+        if (padded_q[called] < 0).any() or qmax >= len(table):
+            raise ValueError("expand_call_units: a called cell's quality is outside the quality table")
+        p_call = table[np.where(called, padded_q, 0)][..., None]
+        p_other = (1.0 - p_call) / 3.0
     reads = np.where(padded[..., None] == allele, p_call, p_other)
     reads = np.where((padded < 0)[..., None], np.nan, reads)
     reads = np.where(allele >= nal[:, None, :, None], 0.0, reads)

@@ -8,7 +8,8 @@ Differences, by design: `--cores N` sizes the pool of host threads that inflate 
 reference forks N processes over blocks of loci; here a block of loci is one GPU launch); with several ranks
 (`python -m torch.distributed.run --nproc-per-node N -m mchap_amd ...`, one rank per GPU) the targets / records are
 sharded over the ranks and rank 0 writes the one VCF; `--reference` may name a FASTA whose file is absent when its
-`.fai` index is present (contig lengths for the header; unknown reference bases are written as N)."""
+`.fai` index is present (contig lengths for the header; unknown reference bases are written as N); `--block-path
+{auto,off,on,wide}` chooses the host path of a block of targets / records (the block_path keyword of the programs)."""
 import argparse
 import sys
 
@@ -128,7 +129,15 @@ def build_parser(program):
     p.add_argument("--report", type=str, nargs="*", default=[],
                    help="extra fields: AFPRIOR ACP AFP AOP AOPSUM GP GL SNVDP, optionally with an INFO/ or FORMAT/ prefix")
     p.add_argument("--cores", type=int, nargs=1, default=[1], help="host threads reading the alignment files")
+    p.add_argument("--block-path", type=str, default="auto", choices=sorted(BLOCK_PATHS),
+                   help="(not a reference flag) host path of a block of targets / records: auto = the program's default, off = locus "
+                        "by locus, on = as array operations over the block (fails for inputs that path does not take), wide = that "
+                        "path with --use-base-phred-scores and --sample-pool too")
     return p
+
+
+# --block-path -> the block_path keyword of application.assemble / call / call_exact
+BLOCK_PATHS = {"auto": None, "off": False, "on": True, "wide": "wide"}
 
 
 def _ranks():
@@ -178,6 +187,7 @@ def run(argv, out=None):
                                     skip_duplicates=args.skip_duplicates, skip_qcfail=args.skip_qcfail,
                                     skip_supplementary=args.skip_supplementary, workers=args.cores[0])
     seed = None
+    block_path = BLOCK_PATHS[args.block_path]
     if program == "assemble":
         if args.targets[0] is not None and args.region[0] is not None:
             raise ValueError("Cannot combine --targets and --region arguments.")
@@ -195,7 +205,8 @@ def run(argv, out=None):
             temperatures=io.sample_temperatures(args.mcmc_temperatures, samples), targets=targets, shard=shard,
             fix_homozygous=args.mcmc_fix_homozygous[0], recombination_step_probability=args.mcmc_recombination_step_probability[0],
             partial_dosage_step_probability=args.mcmc_partial_dosage_step_probability[0],
-            dosage_step_probability=args.mcmc_dosage_step_probability[0], llk_cache_threshold=args.mcmc_llk_cache_threshold[0])
+            dosage_step_probability=args.mcmc_dosage_step_probability[0], llk_cache_threshold=args.mcmc_llk_cache_threshold[0],
+            block_path=block_path)
     else:
         if args.haplotypes[0] is None:
             raise ValueError("--haplotypes is required")
@@ -205,13 +216,14 @@ def run(argv, out=None):
         contigs = io.vcf_contigs(args.haplotypes[0]) or (io.bam_header(next(iter(source.bams)))[0] if source.bams else [])
         if program == "call-exact":
             records = application.call_exact(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
-                                             inbreeding=inbreeding, filter_input_haplotypes=args.filter_input_haplotypes[0], shard=shard)
+                                             inbreeding=inbreeding, filter_input_haplotypes=args.filter_input_haplotypes[0], shard=shard,
+                                             block_path=block_path)
         else:
             seed = args.mcmc_seed[0]
             records = application.call(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
                                        inbreeding=inbreeding, steps=args.mcmc_steps[0], burn=args.mcmc_burn[0], chains=args.mcmc_chains[0],
                                        seed=seed, incongruence_threshold=args.mcmc_chain_incongruence_threshold[0],
-                                       filter_input_haplotypes=args.filter_input_haplotypes[0], shard=shard)
+                                       filter_input_haplotypes=args.filter_input_haplotypes[0], shard=shard, block_path=block_path)
     lines = list(records) if world > 1 else records
     if world > 1:
         # the only exchange: every rank's formatted record lines to rank 0, which writes them in target order (the shards

@@ -57,4 +57,47 @@ int mchap_call_reads_from_calls_device(int n_units, const int8_t *calls, const i
   return mchap::fail(MCHAP_ERR_HIP, "call_reads_kernel: %s", hipGetErrorString(e));
 }
 
+int mchap_call_reads_from_calls_quals_device(int n_units, const int8_t *calls, const int16_t *quals, const int64_t *counts,
+                                             const int64_t *unit_rows, const int64_t *unit_call_off, const int64_t *unit_count_off,
+                                             const int8_t *n_alleles, int n_reads, int n_pos, int max_allele, const double *p_call,
+                                             const double *p_other, int n_qual, double *reads, int64_t *read_counts, void *stream) {
+  if (n_units <= 0) return MCHAP_OK;
+  if (n_reads < 1 || n_pos < 1 || max_allele < 1 || n_qual < 1)
+    return mchap::fail(MCHAP_ERR_BAD_ARG, "call reads: n_reads, n_pos, max_allele and n_qual must be at least 1");
+  // (calls / quals / counts may be NULL when no unit has a row: they are then never read)
+  if (!unit_rows || !unit_call_off || !unit_count_off || !n_alleles || !p_call || !p_other || !reads || !read_counts ||
+      (calls && !quals))
+    return mchap::fail(MCHAP_ERR_BAD_ARG, "call reads: NULL buffer");
+  mchap::CallReadsQualsParams Q;
+  mchap::CallReadsParams &P = Q.base;
+  P.calls = calls;
+  P.counts = counts;
+  P.unit_rows = unit_rows;
+  P.unit_call_off = unit_call_off;
+  P.unit_count_off = unit_count_off;
+  P.n_alleles = n_alleles;
+  P.n_units = n_units;
+  P.R = n_reads;
+  P.M = n_pos;
+  P.A = max_allele;
+  P.p_call = P.p_other = 0.0;
+  P.reads = reads;
+  P.read_counts = read_counts;
+  Q.quals = quals;
+  Q.p_call = p_call;
+  Q.p_other = p_other;
+  Q.n_qual = n_qual;
+  const int64_t rows = (int64_t)n_units * n_reads;
+  const int64_t cells = rows * ((int64_t)n_pos * max_allele);
+  const char *wide = getenv("MCHAP_HIP_CALL_READS_WIDE");   // (as above)
+  if (cells < ((int64_t)1 << 32) && !(wide && wide[0] == '1'))
+    hipLaunchKernelGGL(mchap::call_reads_quals_kernel<uint32_t>, dim3(grid_of(cells)), dim3(mchap::CALL_READS_THREADS), 0, (hipStream_t)stream, Q);
+  else
+    hipLaunchKernelGGL(mchap::call_reads_quals_kernel<int64_t>, dim3(grid_of(cells)), dim3(mchap::CALL_READS_THREADS), 0, (hipStream_t)stream, Q);
+  hipLaunchKernelGGL(mchap::call_read_counts_kernel, dim3(grid_of(rows)), dim3(mchap::CALL_READS_THREADS), 0, (hipStream_t)stream, P);
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return MCHAP_OK;
+  return mchap::fail(MCHAP_ERR_HIP, "call_reads_quals_kernel: %s", hipGetErrorString(e));
+}
+
 }  // extern "C"

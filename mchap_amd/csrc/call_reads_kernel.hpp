@@ -62,6 +62,54 @@ __global__ __launch_bounds__(CALL_READS_THREADS) static void call_reads_kernel(c
   }
 }
 
+// The same tensor with base qualities in use (mchap_call_reads_from_calls_quals_device): a called cell of quality q gives its allele
+// p_call[q] and every other allele p_other[q] -- two float64 tables of n_qual entries the host computed as as_probabilistic does
+// (p_other[q] = (1 - p_call[q]) / 3), so here too the device does no arithmetic on probabilities and the tensor is the host's bit for
+// bit.  Same shape of kernel: one lane per output double (512 consecutive bytes a wavefront), grid-stride over the same capped grid,
+// the cell index divided in 32 or 64 bits.  A lane loads its call byte and its n_alleles byte; for a called cell also the int16
+// quality (the lanes of a cell's A alleles share it) and ONE table entry, its index clamped into [0, n_qual) so that no input reads
+// outside the tables (the host has checked the qualities before the upload).  NOT MEASURED: whether the stores, the two integer
+// divisions or the table gathers (a few hundred distinct entries at most: they should stay in cache) bound this kernel.
+struct CallReadsQualsParams {
+  CallReadsParams base;           // (p_call / p_other of the base are not used)
+  const int16_t *quals;           // laid out like base.calls
+  const double *p_call;           // [n_qual]
+  const double *p_other;          // [n_qual]
+  int n_qual;                     // >= 1
+};
+
+template <typename Index>
+__global__ __launch_bounds__(CALL_READS_THREADS) static void call_reads_quals_kernel(const CallReadsQualsParams Q) {
+  const CallReadsParams &P = Q.base;
+  const uint32_t MA = (uint32_t)P.M * (uint32_t)P.A;
+  const int64_t total = P.n_units * P.R * (int64_t)MA;
+  const int64_t stride = (int64_t)gridDim.x * CALL_READS_THREADS;
+  const double gap = __builtin_nan("");
+  for (int64_t i64 = (int64_t)blockIdx.x * CALL_READS_THREADS + threadIdx.x; i64 < total; i64 += stride) {
+    const Index i = (Index)i64;
+    const Index row = i / (Index)MA;                           // u * R + r
+    const uint32_t in_row = (uint32_t)(i - row * (Index)MA);   // j * A + a
+    const uint32_t j = in_row / (uint32_t)P.A;
+    const int a = (int)(in_row - j * (uint32_t)P.A);
+    const Index ui = row / (Index)P.R;
+    const int64_t u = (int64_t)ui;
+    const int64_t r = (int64_t)(row - ui * (Index)P.R);
+    double v = gap;  // a padding row: NaN in every cell
+    if (r < P.unit_rows[u]) {
+      const int64_t e = P.unit_call_off[u] + r * P.M + j;
+      const int call = P.calls[e];
+      const int n = P.n_alleles[u * P.M + j];
+      if (call >= 0) {
+        int q = Q.quals[e];
+        q = q < 0 ? 0 : (q >= Q.n_qual ? Q.n_qual - 1 : q);
+        v = a == call ? Q.p_call[q] : Q.p_other[q];
+      }
+      if (a >= n) v = 0.0;  // (last, as in call_reads_kernel)
+    }
+    P.reads[i64] = v;
+  }
+}
+
 // read_counts[u][r]: the row's count, 0 for a padding row -- one lane per count
 __global__ __launch_bounds__(CALL_READS_THREADS) static void call_read_counts_kernel(const CallReadsParams P) {
   const int64_t total = P.n_units * P.R;

@@ -304,17 +304,69 @@ def call_reads_from_calls(calls, counts, unit_rows, unit_call_off, unit_count_of
     return d_reads, d_counts
 
 
+def call_reads_from_calls_quals(calls, quals, counts, unit_rows, unit_call_off, unit_count_off, n_alleles, n_reads, max_allele,
+                                error_rate=0.0024, n_qual=None, device=None):
+    """call_reads_from_calls with base qualities in use (mchap_call_reads_from_calls_quals_device): quals int16, laid out like calls.
+    The two probability tables -- p_call[q] = prob_of_qual(q) * (1 - error_rate) and p_other[q] = (1 - p_call[q]) / 3, formed as
+    encoding.encode_read_distributions / as_probabilistic form them -- hold n_qual entries: by default one more than the largest
+    quality of a called cell of the units.  Returns the same pair of torch tensors: encoding.encode_read_distributions of every
+    unit's rows with their qualities, padded to n_reads with NaN rows of count 0."""
+    from .blockpath import _ragged_arange, qual_prob_table
+
+    torch = _torch()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    calls = np.ascontiguousarray(calls, dtype=np.int8).reshape(-1)
+    quals = np.ascontiguousarray(quals, dtype=np.int16).reshape(-1)
+    counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    rows = np.ascontiguousarray(unit_rows, dtype=np.int64)
+    c_off = np.ascontiguousarray(unit_call_off, dtype=np.int64)
+    n_off = np.ascontiguousarray(unit_count_off, dtype=np.int64)
+    nal = np.ascontiguousarray(n_alleles, dtype=np.int8)
+    U, M = nal.shape
+    R, A = int(n_reads), int(max_allele)
+    if not (rows.shape == c_off.shape == n_off.shape == (U,)) or R < 1 or M < 1 or A < 1 or len(quals) != len(calls):
+        raise AssertionError("call_reads_from_calls_quals: per-unit arrays of one length, as many qualities as calls, n_reads, positions "
+                             "and max_allele at least 1")
+    # (the kernel reads calls / quals / counts at these offsets: checked here, where the arrays are still on the host)
+    if U and (rows.min() < 0 or rows.max() > R or c_off.min() < 0 or n_off.min() < 0 or (c_off + rows * M).max() > len(calls)
+              or (n_off + rows).max() > len(counts)):
+        raise AssertionError("call_reads_from_calls_quals: a unit's rows lie outside calls / counts, or exceed n_reads")
+    # ... and the tables at the qualities of the units' called cells
+    owner, k = _ragged_arange(rows * M)
+    used = c_off[owner] + k
+    q_called = quals[used][calls[used] >= 0]
+    n_qual = int(q_called.max(initial=0)) + 1 if n_qual is None else int(n_qual)
+    if n_qual < 1 or (len(q_called) and (q_called.min() < 0 or q_called.max() >= n_qual)):
+        raise AssertionError("call_reads_from_calls_quals: the quality of a called cell lies outside the table (0 <= q < %d)" % n_qual)
+    p_call = qual_prob_table(error_rate, n_qual)     # (as encoding.encode_read_distributions / as_probabilistic form them)
+    p_other = (1.0 - p_call) / 3.0
+    up = lambda a: torch.from_numpy(a).to(dev) if a.size else None  # noqa: E731
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    d_in = [up(a) for a in (calls, quals, counts, rows, c_off, n_off, nal.reshape(-1))]
+    d_tab = [up(np.ascontiguousarray(p_call)), up(np.ascontiguousarray(p_other))]
+    d_reads = torch.empty((U, R, M, A), dtype=torch.float64, device=dev)
+    d_counts = torch.empty((U, R), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().mchap_call_reads_from_calls_quals_device(
+            U, *[p(t) for t in d_in], R, M, A, p(d_tab[0]), p(d_tab[1]), n_qual, p(d_reads), p(d_counts), C.c_void_p(stream)))
+    # (the inputs were allocated and are consumed on this stream: the allocator reuses them only for later work of the same stream)
+    return d_reads, d_counts
+
+
 class CompactCallReads:
     """The reads of a shape group of `mchap call` / `mchap call-exact` in the compact form of blockpath.call_unit_inputs, standing
     where the float64 [U, n_reads, M, max_allele] tensor does: `shape`, `len`, indexing and numpy conversion give that tensor
     (formed on the host by blockpath.expand_call_units when someone asks for it: a stand-in sampler of the tests, the host classes
     on downloaded traces), `counts` the [U, n_reads] counts in the same way, and on_device() both as device tensors formed there
-    from the int8 calls -- what application._group_inputs hands to CallingMCMC.start_batch_summaries and, through _run_exact_groups, to ExactDeviceBatch."""
+    from the int8 calls (and, where the group comes with base qualities, `quals`: int16 laid out like the calls) -- what application._group_inputs hands to CallingMCMC.start_batch_summaries and, through _run_exact_groups, to ExactDeviceBatch."""
 
     ndim, dtype = 4, np.dtype(np.float64)
 
-    def __init__(self, calls, counts, unit_rows, unit_call_off, unit_count_off, n_alleles, n_reads, max_allele, error_rate=0.0024):
+    def __init__(self, calls, counts, unit_rows, unit_call_off, unit_count_off, n_alleles, n_reads, max_allele, error_rate=0.0024,
+                 quals=None):
         self.compact = (calls, counts, unit_rows, unit_call_off, unit_count_off, n_alleles)
+        self.quals = quals
         self.n_reads, self.max_allele, self.error_rate = int(n_reads), int(max_allele), error_rate
         self.shape = (n_alleles.shape[0], self.n_reads, n_alleles.shape[1], self.max_allele)
         self.counts = _CompactCallCounts(self)
@@ -322,13 +374,16 @@ class CompactCallReads:
 
     def on_device(self, device=None):
         """(reads, read_counts) device tensors, the fill enqueued on torch's current stream."""
+        if self.quals is not None:
+            return call_reads_from_calls_quals(self.compact[0], self.quals, *self.compact[1:], self.n_reads, self.max_allele,
+                                               error_rate=self.error_rate, device=device)
         return call_reads_from_calls(*self.compact, self.n_reads, self.max_allele, error_rate=self.error_rate, device=device)
 
     def on_host(self):
         if self._host is None:
             from .blockpath import expand_call_units
 
-            self._host = expand_call_units(*self.compact, self.n_reads, self.max_allele, error_rate=self.error_rate)
+            self._host = expand_call_units(*self.compact, self.n_reads, self.max_allele, error_rate=self.error_rate, quals=self.quals)
         return self._host
 
     def __len__(self):
@@ -582,8 +637,8 @@ class DenovoRaggedBatch(_OwnBuffers):
         self.cfg.cache_epoch = _lib.next_cache_epoch()
         if self.d_reads is None:
             _lib.check(L.mchap_denovo_fit_batch_calls_device(
-                C.byref(self.cfg), self.n_units, self._p(self.d_units), _lib.ptr(self.units_host), self._p(self.d_calls), None,
-                self._p(self.d_qual_prob), 1, self._p(self.d_counts), self._p(self.d_nalleles), None, self._p(self.d_trace),
+                C.byref(self.cfg), self.n_units, self._p(self.d_units), _lib.ptr(self.units_host), self._p(self.d_calls),
+                self._p(self.d_quals), self._p(self.d_qual_prob), int(self.qual_prob_len), self._p(self.d_counts), self._p(self.d_nalleles), None, self._p(self.d_trace),
                 self._p(self.d_llks), self._p(self.d_fixed), self._p(self.d_status), self._p(self.d_ws), C.c_int64(self.ws_bytes),
                 C.c_void_p(stream)))
             return
@@ -594,12 +649,14 @@ class DenovoRaggedBatch(_OwnBuffers):
 
     @classmethod
     def from_calls(cls, model, calls, reads_off, n_reads, n_pos, max_allele, ploidy, counts, counts_off, n_alleles, nalleles_off,
-                   inbreeding=None, error_rate=0.0024, device=None):
+                   inbreeding=None, error_rate=0.0024, device=None, quals=None):
         """The same batch from the compact input (reference encoders: encoding/integer/transcode.py:16-77 with base qualities
         ignored, as the programs do by default), built with array operations only -- one row of every array per unit:
         calls int8 (all units' [n_reads, n_pos] matrices of allele calls, < 0 = gap, unit u at reads_off[u]), counts int64 (unit u's
         n_reads[u] counts at counts_off[u]; -1 = none), n_alleles int8 (unit u's n_pos[u] values at nalleles_off[u]; units may
-        share them), inbreeding float [U] (NaN = none) or None."""
+        share them), inbreeding float [U] (NaN = none) or None.  quals: None, or -- base qualities in use -- int16 laid out like calls:
+        a called cell of quality q then gives its allele prob_of_qual(q) * (1 - error_rate) (reference io/bam.py:280-288), read on
+        the device from a table of as many entries as the largest quality asks for."""
         self = cls.__new__(cls)
         torch = _torch()
         self.torch = torch
@@ -631,7 +688,18 @@ class DenovoRaggedBatch(_OwnBuffers):
         self.d_units = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(dev)
         self.d_reads = None
         self.d_calls = torch.from_numpy(np.ascontiguousarray(calls, dtype=np.int8)).to(dev)
-        self.d_qual_prob = torch.from_numpy(np.array([1.0 - error_rate], dtype=np.float64)).to(dev)
+        self.d_quals, table = None, np.array([1.0 - error_rate], dtype=np.float64)
+        if quals is not None:
+            from .blockpath import qual_prob_table
+
+            quals = np.ascontiguousarray(quals, dtype=np.int16)
+            assert quals.shape == np.shape(calls)
+            if (quals[np.asarray(calls) >= 0] < 0).any():
+                raise AssertionError("DenovoRaggedBatch.from_calls: a called cell has a negative quality")
+            self.d_quals = torch.from_numpy(quals).to(dev)
+            table = qual_prob_table(error_rate, int(quals.max(initial=0)) + 1)
+        self.qual_prob_len = len(table)
+        self.d_qual_prob = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(dev)
         self.d_counts = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int64)).to(dev) if len(counts) else None
         self.d_nalleles = torch.from_numpy(np.ascontiguousarray(n_alleles, dtype=np.int8)).to(dev)
         self.d_trace = torch.empty(int(t.sum()) * self.wph, dtype=torch.int64, device=dev)

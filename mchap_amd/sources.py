@@ -162,11 +162,25 @@ def encode_reads(locus, chars, quals, error_rate=0.0024, use_phred=False):
     return dict(chars=chars, calls=calls, depth=depth, dists=uniq, counts=counts)
 
 
-def _block_path_takes(source):
+def _block_path_takes(source, wide=False):
     """The array path of a block reads every sample from one alignment file held whole in memory (or from pileup matrices the
-    caller has already), base qualities ignored."""
+    caller has already), base qualities ignored.  wide (block_path="wide"): base qualities in use and pooled samples -- every
+    pool one or more (read group, file) pairs -- are taken too; the files still have to be BAM files held whole."""
     from .io import BamFile
 
+    if wide:
+        if isinstance(source, MatrixSource):
+            return True
+        if not isinstance(source, ReadSource):
+            return False
+        for pairs in source.pools.values():
+            if len(pairs) < 1:
+                return False
+            for _, path in pairs:
+                bam = source.bams[path]
+                if not isinstance(bam, BamFile) or (bam.index is not None and len(bam.data) > source.WHOLE_FILE_BYTES):
+                    return False
+        return True
     if isinstance(source, MatrixSource):
         return not source.use_phred
     if not isinstance(source, ReadSource) or source.use_phred:
@@ -183,7 +197,9 @@ def _block_path_takes(source):
 def _block_encodings(loci, source, samples, timings=None, inflate_together=False):
     """blockpath.extract_block / encode_block over the loci of a block (records of call / call-exact, targets of assemble), once per
     sample (tables and look-up table shared): dict(encs [per sample], si {sample: index}, nal int8 alleles of every SNV, tables,
-    error_rate).  timings: a dict whose "bam_parse_s" receives the seconds spent inflating and parsing files on their first use;
+    error_rate, qtable).  A pooled sample's pile is its pairs' piles concatenated (blockpath.concat_piles; a (read group, file) pair
+    shared by several pools is extracted once); qtable: blockpath.qual_prob_table over the block's qualities when the source uses
+    them (the rows are then de-duplicated as their float rows are), else None.  timings: a dict whose "bam_parse_s" receives the seconds spent inflating and parsing files on their first use;
     inflate_together: files not parsed yet are inflated and walked side by side when the source has workers for it."""
     import time as _time
 
@@ -199,7 +215,7 @@ def _block_encodings(loci, source, samples, timings=None, inflate_together=False
 
     if inflate_together and isinstance(source, ReadSource) and source.workers > 1:
         # (zlib and the library's record walk release the interpreter lock)
-        todo = [b for b in dict.fromkeys(source.bams[source.pools[s_][0][1]] for s_ in samples) if getattr(b, "_all", 0) is None]
+        todo = [b for b in dict.fromkeys(source.bams[path] for s_ in samples for _, path in source.pools[s_]) if getattr(b, "_all", 0) is None]
         if len(todo) > 1:
             from concurrent.futures import ThreadPoolExecutor
 
@@ -207,16 +223,26 @@ def _block_encodings(loci, source, samples, timings=None, inflate_together=False
             with ThreadPoolExecutor(max_workers=min(source.workers, len(todo))) as ex:
                 list(ex.map(lambda b: b.columns(), todo))
             parsed(tp)
-    encs = []
-    for sample in samples:
-        if isinstance(source, MatrixSource):
-            pile = bp.pile_from_matrices(loci, [source.codes(l.name, sample) for l in loci], tables=tables)
-        else:
-            name, path = source.pools[sample][0]
+    extracted = {}
+
+    def pair_pile(name, path):
+        got = extracted.get((name, path))
+        if got is None:
             tp = _time.perf_counter()
             cols = source.bams[path].columns()   # (the first use of a file inflates and parses it)
             parsed(tp)
-            pile = bp.extract_block(loci, cols, name, tables=tables, **source.filter)
-        encs.append(bp.encode_block(loci, pile, lut))
+            got = extracted[(name, path)] = bp.extract_block(loci, cols, name, tables=tables, **source.filter)
+        return got
+
+    piles = []
+    for sample in samples:
+        if isinstance(source, MatrixSource):
+            piles.append(bp.pile_from_matrices(loci, [source.codes(l.name, sample) for l in loci], tables=tables))
+        else:
+            piles.append(bp.concat_piles([pair_pile(name, path) for name, path in source.pools[sample]]))
+    qtable = None
+    if source.use_phred:
+        qtable = bp.qual_prob_table(source.error_rate, max((int(p.quals.max(initial=0)) for p in piles), default=0) + 1)
+    encs = [bp.encode_block(loci, pile, lut, **({} if qtable is None else dict(quality_table=qtable))) for pile in piles]
     nal = np.fromiter((a for l in loci for a in l.n_alleles), dtype=np.int8, count=n_snv)
-    return dict(encs=encs, si={s: i for i, s in enumerate(samples)}, nal=nal, tables=tables, error_rate=source.error_rate)
+    return dict(encs=encs, si={s: i for i, s in enumerate(samples)}, nal=nal, tables=tables, error_rate=source.error_rate, qtable=qtable)

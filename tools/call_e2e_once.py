@@ -5,8 +5,9 @@ targets x `samples` samples, the programs re-call every sample against it (files
   * `call` and `call-exact` through mchap_amd.application with block_path=False (reads fetched and encoded record by record, the
     float tensors filled on the host) and with block_path=True (the block path: mchap_amd/blockpath.py, int8 calls uploaded, the read
     tensors formed on the device), `reps` times each: the median rate of both and whether the record lines are equal.
-Usage: python tools/call_e2e_once.py [loci] [samples] [reps] [call|call-exact|both] [profile]
-(`profile`: a cProfile of one more run of each program on the block path, by cumulative time)"""
+Usage: python tools/call_e2e_once.py [loci] [samples] [reps] [call|call-exact|both] [profile] [phred]
+(`profile`: a cProfile of one more run of each program on the block path, by cumulative time; `phred`: the two legs with base
+qualities in use -- per record against block_path="wide", int16 qualities uploaded with the calls -- and nothing else)"""
 import io as _io, os, sys, time, tempfile, shutil, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mchap_amd import application, cli, synth
@@ -16,7 +17,8 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 300
 ns = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 reps = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 which = sys.argv[4] if len(sys.argv) > 4 else "both"
-profile = len(sys.argv) > 5 and sys.argv[5] == "profile"
+profile = "profile" in sys.argv[5:]
+phred = "phred" in sys.argv[5:]
 HAS_BLOCK_PATH = "block_path" in application.call.__code__.co_varnames   # (the same script measures a commit without it)
 d = tempfile.mkdtemp(prefix="mchap_call_e2e_")
 try:
@@ -25,7 +27,7 @@ try:
     out = _io.StringIO()
     cli.run(["mchap_amd", "assemble", "--bam"] + job["bams"] + ["--targets", job["bed"], "--variants", job["vcf"], "--reference", job["fasta"], "--ploidy", "4"], out)
     open(vcf, "w").write(out.getvalue())
-    if which in ("both", "call"):
+    if which in ("both", "call") and not phred:
         argv = ["mchap_amd", "call", "--bam"] + job["bams"] + ["--haplotypes", vcf, "--ploidy", "4"]
         device = CallingMCMC.start_batch_summaries
 
@@ -47,12 +49,12 @@ try:
         print("same records:", texts["device summaries"] == texts["host classes"])
 
     # ---- the block path against the per-record path, both programs ----
-    source = application.ReadSource({os.path.basename(b)[:-4]: b for b in job["bams"]})
+    source = application.ReadSource({os.path.basename(b)[:-4]: b for b in job["bams"]}, use_phred=phred)
     for bam in source.bams.values():
         bam.columns()   # (the files inflated and parsed once, outside the timed legs: both paths share the columns)
     programs = [p for p in (("call", application.call), ("call-exact", application.call_exact)) if which in ("both", p[0])]
     for name, fn in programs:
-        legs = (("per record", dict(block_path=False)), ("block path", dict(block_path=True))) if HAS_BLOCK_PATH else (("per record", dict()),)
+        legs = (("per record", dict(block_path=False)), ("block path", dict(block_path="wide" if phred else True))) if HAS_BLOCK_PATH else (("per record", dict()),)
         lines, rate = {}, {}
         for leg, kw in legs:
             list(fn(vcf, source, ploidy=4, **kw))   # (warm-up: streams, allocator, first launches)
