@@ -337,6 +337,32 @@ int mchap_exact_call_batch_device(int n_units, const double *reads, int n_reads,
                                   const double *inbreeding, const double *frequencies, const mchap_exact_out *out,
                                   void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Prior allele frequencies by EM (call-exact --estimate-prior-frequencies): one iteration of
+ *   f'[h] = sum_s K_s freqs_s(f)[h] / sum_s K_s
+ * over the samples s of a record, freqs_s the mean posterior allele frequency of sample s under prior (F_s, f) -- what the
+ * reference writes as INFO/AFP (application/baseclass.py:282-288) and reads back as --prior-frequencies.  The likelihoods do not
+ * depend on f: they are formed once (mchap_exact_call_batch_device, llks64) and stay on the device; an iteration streams them.
+ * Records, not units, carry the frequencies: frequencies [records][stride], record_active [records] (0: frozen, its units are
+ * skipped), and a slab [records][n_samples][stride] that takes every unit's expected allele counts K_s * freqs_s.
+ *
+ * The counts launch, once per iteration for each shape group (n_haps, ploidy) of the sub-block: unit u reads llks64 [u][G],
+ * inbreeding [u] and the row unit_record[u] of `frequencies`, and writes row unit_slot[u] of `slab` (unit_slot = record *
+ * n_samples + sample index: the groups of a record whose samples differ in ploidy fill one record's rows).  Sums in fixed order,
+ * no atomics: equal inputs give equal bits.  `workspace`: mchap_exact_em_workspace_bytes (-1: more than 2^62 genotypes).
+ * Enqueues on `stream`, no synchronisation. */
+int64_t mchap_exact_em_workspace_bytes(int n_units, int n_haps, int ploidy);
+int mchap_exact_em_counts_device(int n_units, const double *llks64, int n_haps, int ploidy, const double *inbreeding,
+                                 const int32_t *unit_record, const int32_t *unit_slot, const double *frequencies, int stride,
+                                 const int32_t *record_active, double *slab, void *workspace, int64_t workspace_bytes, void *stream);
+/* The update launch, once per iteration after the counts launches: for every active record the slab rows summed in sample order
+ * and divided by ploidy_total = sum_s K_s into its row of `frequencies` (record_haps [records]: its number of haplotypes, at most
+ * stride), max |f' - f| into record_delta (or NULL), record_iterations + 1, and record_active = 0 once the maximum is below
+ * `tolerance` or the counter has reached max_iterations: the host only counts the active records now and then to stop launching.
+ * Enqueues on `stream`, no synchronisation. */
+int mchap_exact_em_update_device(int n_records, int n_samples, const int32_t *record_haps, int stride, const double *slab,
+                                 double ploidy_total, double tolerance, int max_iterations, double *frequencies,
+                                 int32_t *record_iterations, int32_t *record_active, double *record_delta, void *stream);
+
 /* Summaries of given posterior arrays [U][G] (calling.exact.posterior_allele_frequencies 332-369, the sum of
  * alternate_dosage_posteriors 372-407 for the array's mode): device pointers, any output may be NULL. */
 int mchap_exact_posterior_summaries_batch_device(int n_units, const double *posteriors, int64_t n_genotypes, int ploidy,

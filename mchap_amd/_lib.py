@@ -195,6 +195,11 @@ def lib():
         L.mchap_denovo_workspace_bytes.restype = C.c_int64
         L.mchap_exact_workspace_bytes.restype = C.c_int64
         L.mchap_exact_workspace_bytes_cached.restype = C.c_int64
+        L.mchap_exact_em_workspace_bytes.restype = C.c_int64
+        L.mchap_exact_em_counts_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + \
+            [C.c_int64, C.c_void_p]
+        L.mchap_exact_em_update_device.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int] + \
+            [C.c_void_p] * 5
         L.mchap_call_mcmc_workspace_bytes.restype = C.c_int64
         L.mchap_call_mcmc_workspace_bytes_for.restype = C.c_int64
         L.mchap_timer_ms.restype = C.c_double
@@ -278,6 +283,9 @@ EXPORTS = [
     "mchap_exact_workspace_bytes",
     "mchap_exact_workspace_bytes_cached",
     "mchap_exact_call_batch_device",
+    "mchap_exact_em_workspace_bytes",
+    "mchap_exact_em_counts_device",
+    "mchap_exact_em_update_device",
     "mchap_exact_posterior_summaries_batch_device",
     "mchap_exact_posterior_summaries",
     "mchap_call_mcmc_workspace_bytes",

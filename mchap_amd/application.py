@@ -214,7 +214,7 @@ def _run_exact_groups(units, ploidy_of, inbreeding_of, full, backend=None):
         G = comb(H + K - 1, K)
         # device bytes per unit: reads + haplotypes + (array form) the float32 / float64 genotype arrays, or (streaming
         # form) the joint values kept between the passes -- the group is cut into chunks that fit the free HBM
-        per_unit = Rmax * M * A * 8 + Rmax * 8 + H * M + (G * 20 if full else G * 8) + 4096
+        per_unit = _exact_unit_bytes(G, 20 if full else 8, Rmax, M, A, H)
         for members in _blocks(group, device_unit_budget(per_unit)):
             # (padded to the chunk's own deepest unit: the kernel sums the reads four to a logarithm, so the padding is part of the bits)
             Rchunk = Rmax if len(members) == len(group) else _group_rows(units, members)
@@ -271,6 +271,226 @@ def _exact_one(calling, sr, haps, ploidy, prior, full):
         sr["dists"], ploidy, haps, read_counts=sr["counts"], prior=prior, return_support_prob=True,
         return_posterior_frequencies=True, return_posterior_occurrence=True)
     return dict(alleles=alleles, gprob=gprob, sprob=sprob, freqs=freqs, occur=occur)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# call-exact --estimate-prior-frequencies: the prior allele frequencies of a record by EM over its samples' posteriors
+# ---------------------------------------------------------------------------------------------------------
+def _exact_unit_bytes(G, per_genotype, R=0, M=0, A=0, H=0):
+    """Device bytes of one unit of the exact caller: its reads, counts and haplotypes (R = 0: none held) and `per_genotype` bytes
+    for each of its G genotypes -- what _run_exact_groups cuts a shape group by and what the frequency estimate's resident
+    likelihoods are counted with."""
+    return R * M * A * 8 + R * 8 + H * M + G * per_genotype + 4096
+
+
+def _em_update(f, acc, ploidy_total, eps):
+    """One update of a record's row: (f', met) with f' = acc / sum of the ploidies and met = max |f' - f| < eps."""
+    new = acc / float(ploidy_total)
+    return new, bool(np.max(np.abs(new - f)) < eps)
+
+
+def estimate_frequencies_host(units, samples, ploidy_of, inbreeding_of, iterations, tolerance, backend, records=None):
+    """The definition of the estimate, on `backend` (an object with the reference's posterior_mode; the oracle in the CPU tests):
+    for every record that needs the kernel, from f_0 = locus.frequencies,
+        f_{t+1}[h] = sum_s K_s freqs_s(f_t)[h] / sum_s K_s
+    over all samples in sample order, freqs_s the mean posterior allele frequency of sample s under prior (F_s, f_t) -- the
+    reference's INFO/AFP fed back as --prior-frequencies; at most `iterations` of them, ending with the first whose
+    max |f_{t+1} - f_t| is below `tolerance` (its result is kept).  Returns {record index: (frequencies, iterations run)}."""
+    out = {}
+    ktot = sum(int(ploidy_of(s)) for s in samples)
+    for ri in (range(len(units)) if records is None else records):
+        unit = units[ri]
+        if not unit["needs_kernel"]:
+            continue
+        locus = unit["locus"]
+        f, it = np.array(locus.frequencies, dtype=np.float64), 0
+        while it < int(iterations):
+            acc = np.zeros(len(f))
+            for s in samples:
+                sr, K = unit["reads"][s], int(ploidy_of(s))
+                freqs = backend.posterior_mode(sr["dists"], K, locus.haplotypes, read_counts=sr["counts"], prior=(inbreeding_of(s), f),
+                                               return_support_prob=True, return_posterior_frequencies=True,
+                                               return_posterior_occurrence=True)[4]
+                acc += K * np.asarray(freqs, dtype=np.float64)
+            f, met = _em_update(f, acc, ktot, tolerance)
+            it += 1
+            if met:
+                break
+        out[ri] = (f, it)
+    return out
+
+
+def _estimate_plan(units, samples, ploidy_of, path=None):
+    """Which records the device estimates how: (sub-blocks of record indices whose likelihoods stay resident, sub-blocks for the
+    recompute path, records not estimated because the library refuses their shape).  A sub-block holds whole records, consecutive,
+    whose units' likelihoods (G * 8 bytes each, _exact_unit_bytes) fit the device budget together; a record whose own likelihoods
+    exceed it is iterated by the recompute path (memory is not a shape limit).  path: None, or "resident" / "recompute" for all."""
+    from math import comb
+
+    from ._lib import MAX_PLOIDY_GENERAL
+
+    if path not in (None, "resident", "recompute"):
+        raise ValueError("estimate_path: None, 'resident' or 'recompute'")
+    budget = device_unit_budget(1, most=1 << 62)
+    resident, recompute, refused = [], [], []
+    cur, cur_bytes = [], 0
+    for ri, unit in enumerate(units):
+        if not unit["needs_kernel"]:
+            continue
+        H = len(unit["locus"].haplotypes)
+        Ks = [int(ploidy_of(s)) for s in samples]
+        if max(Ks) > MAX_PLOIDY_GENERAL or any(comb(H + K - 1, K) >= 1 << 62 for K in Ks):
+            refused.append(ri)
+            continue
+        cost = sum(_exact_unit_bytes(comb(H + K - 1, K), 8) for K in Ks)
+        if path == "recompute" or (path is None and cost > budget):
+            recompute.append(ri)
+            continue
+        if cur and cur_bytes + cost > budget:
+            resident.append(cur)
+            cur, cur_bytes = [], 0
+        cur.append(ri)
+        cur_bytes += cost
+    if cur:
+        resident.append(cur)
+    # the recompute path holds the reads of a sub-block's units, not their likelihoods: as many records as _RECOMPUTE_RECORDS
+    return resident, list(_blocks(recompute, _RECOMPUTE_RECORDS)) if recompute else [], refused
+
+
+_RECOMPUTE_RECORDS = 256   # records of a sub-block of the recompute path (their units' reads and workspaces are resident)
+ESTIMATE_POLL = 4          # iterations between two looks at the number of active records (the result does not depend on it)
+
+
+def _estimate_group_batches(units, members, shape, inbreeding_of, per_genotype, prior):
+    """The device batches of a shape group's units for the estimate, cut by the free HBM as _run_exact_groups cuts them: yields
+    (members of the chunk, batch) -- or (members, None) for a chunk whose shape the library refuses."""
+    from math import comb
+
+    from .device import ExactDeviceBatch
+
+    M, A, H, K = shape
+    Rmax = _group_rows(units, members)
+    per_unit = _exact_unit_bytes(comb(H + K - 1, K), per_genotype, Rmax, M, A, H)
+    for chunk in _blocks(members, device_unit_budget(per_unit)):
+        Rchunk = Rmax if len(chunk) == len(members) else _group_rows(units, chunk)
+        reads, counts, haps, pr = _group_inputs(units, chunk, shape, Rchunk, inbreeding_of)
+        try:
+            if hasattr(reads, "on_device"):
+                reads, counts = reads.on_device()
+                yield chunk, ExactDeviceBatch.from_device_reads(reads, K, haps, counts, pr if prior else None, cache_joint=False)
+            else:
+                yield chunk, ExactDeviceBatch(reads, K, haps, counts, pr if prior else None, cache_joint=False)
+        except NotImplementedError:
+            yield chunk, None
+
+
+def _estimate_resident(units, recs, samples, ploidy_of, inbreeding_of, iterations, tolerance, poll):
+    """A sub-block on the resident path: the likelihoods of every shape group once (llks64 alone), then the iterations on the
+    device.  Returns {record index: (frequencies, iterations)}; a record with a refused group is left out."""
+    from .device import ExactFrequencyEstimate
+
+    pos = {ri: i for i, ri in enumerate(recs)}
+    si = {s: i for i, s in enumerate(samples)}
+    Hs = np.array([len(units[ri]["locus"].haplotypes) for ri in recs], dtype=np.int32)
+    f0 = np.zeros((len(recs), int(Hs.max())))
+    for i, ri in enumerate(recs):
+        f0[i, :Hs[i]] = units[ri]["locus"].frequencies
+    est = ExactFrequencyEstimate(Hs, f0, len(samples), sum(int(ploidy_of(s)) for s in samples))
+    refused = set()
+    sub = [units[ri] for ri in recs]
+    for shape, group in _shape_groups(sub, ploidy_of).items():
+        M, A, H, K = shape
+        for chunk, batch in _estimate_group_batches(sub, group, shape, inbreeding_of, 8, prior=False):
+            try:
+                if batch is None:
+                    raise NotImplementedError
+                llks = batch.run_llks64()
+            except NotImplementedError:
+                refused.update(recs[i] for i, _ in chunk)
+                continue
+            est.add_group(llks, H, K, [inbreeding_of(s) for _, s in chunk], [i for i, _ in chunk], [si[s] for _, s in chunk])
+            del batch   # (the reads go back to the allocator; the likelihoods stay with the estimate)
+    est.freeze([pos[ri] for ri in sorted(refused)])
+    est.run(iterations, tolerance, poll)
+    fr, its = est.results()
+    return {ri: (fr[i, :Hs[i]].copy(), int(its[i])) for i, ri in enumerate(recs) if ri not in refused}
+
+
+def _estimate_recompute(units, recs, samples, ploidy_of, inbreeding_of, iterations, tolerance):
+    """A sub-block on the recompute path: the same iteration driven from the host, every iteration the streaming form's two
+    passes over the reads under the current prior (ExactDeviceBatch.run_freqs), the update on the host."""
+    sub = [units[ri] for ri in recs]
+    ktot = sum(int(ploidy_of(s)) for s in samples)
+    Kof = {s: int(ploidy_of(s)) for s in samples}
+    f = [np.array(u["locus"].frequencies, dtype=np.float64) for u in sub]
+    its = [0] * len(sub)
+    active = [int(iterations) > 0] * len(sub)
+    batches, refused = [], set()
+    for shape, group in _shape_groups(sub, ploidy_of).items():
+        for chunk, batch in _estimate_group_batches(sub, group, shape, inbreeding_of, 0, prior=True):
+            if batch is None:
+                refused.update(i for i, _ in chunk)
+            else:
+                batches.append((chunk, batch))
+    for i in refused:
+        active[i] = False
+    while any(active):
+        got = {}
+        for chunk, batch in batches:
+            if not any(active[i] for i, _ in chunk):
+                continue
+            try:
+                fq = batch.run_freqs(np.stack([f[i] for i, _ in chunk]))
+            except NotImplementedError:
+                for i, _ in chunk:
+                    active[i] = False
+                    refused.add(i)
+                continue
+            for j, key in enumerate(chunk):
+                got[key] = fq[j]
+        for i in range(len(sub)):
+            if not active[i]:
+                continue
+            acc = np.zeros(len(f[i]))
+            for s in samples:   # (sample order, as the definition)
+                acc += Kof[s] * got[(i, s)]
+            f[i], met = _em_update(f[i], acc, ktot, tolerance)
+            its[i] += 1
+            active[i] = not (met or its[i] >= int(iterations))
+    return {ri: (f[i], its[i]) for i, ri in enumerate(recs) if i not in refused}
+
+
+def estimate_prior_frequencies(units, samples, ploidy_of, inbreeding_of, iterations, tolerance=1e-6, backend=None, path=None,
+                               poll=None):
+    """The estimate for a block of records (what _exact_units returned): every estimated record's locus.frequencies is replaced by
+    its estimate and unit["emit"] set to the iterations run (None where nothing was estimated: an invalid record, a single
+    haplotype, a shape the library refuses).  backend: the definition on that object (estimate_frequencies_host); None = the
+    device, resident likelihoods where they fit and the recompute path where not (path: force one).  Returns {record index:
+    (frequencies, iterations)}."""
+    for s in samples:
+        if inbreeding_of(s) is None:
+            raise ValueError("estimate_frequencies needs an inbreeding value for every sample (--use-dirmul-prior): the flat genotype "
+                             "prior has no allele frequencies to estimate")
+    if int(iterations) < 0 or not float(tolerance) >= 0.0:
+        raise ValueError("estimate_frequencies: iterations >= 0 and tolerance >= 0")
+    for unit in units:
+        unit["emit"] = None
+    if backend is not None:
+        if path not in (None, "resident", "recompute"):
+            raise ValueError("estimate_path: None, 'resident' or 'recompute'")
+        out = estimate_frequencies_host(units, samples, ploidy_of, inbreeding_of, iterations, tolerance, backend)
+    else:
+        resident, recompute, _ = _estimate_plan(units, samples, ploidy_of, path)
+        out = {}
+        for recs in resident:
+            out.update(_estimate_resident(units, recs, samples, ploidy_of, inbreeding_of, iterations, tolerance,
+                                          ESTIMATE_POLL if poll is None else poll))
+        for recs in recompute:
+            out.update(_estimate_recompute(units, recs, samples, ploidy_of, inbreeding_of, iterations, tolerance))
+    for ri, (f, it) in out.items():
+        units[ri]["locus"].frequencies = np.asarray(f, dtype=np.float64)
+        units[ri]["emit"] = int(it)
+    return out
 
 
 def _per_sample(value, samples):
@@ -346,7 +566,8 @@ def _blocks(items, n):
 
 def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.0024, use_base_phred_scores=False,
                prior_frequencies_tag=None, inbreeding=None, calling=None, filter_input_haplotypes=None, read_kw=None,
-               records_per_block=4096, shard=None, block_path=None):
+               records_per_block=4096, shard=None, block_path=None, estimate_frequencies=None, estimate_tolerance=1e-6,
+               estimate_path=None):
     """`mchap call-exact` over a VCF of known haplotypes: yields one VCF record line per input record (no header).
     sample_bams: ordered mapping sample name -> BAM path (or pool -> [(sample, path)], or a ReadSource); ploidy /
     inbreeding: a value or {sample: value}.  The records are processed in blocks: the (record x sample) units of a block
@@ -363,7 +584,15 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
     it and CALL_BLOCK_PATH_DEFAULT is set, else record by record; "wide" = the block path for a wider set of inputs -- base
     qualities in use (int8 calls and int16 qualities are uploaded, rows are de-duplicated as their float rows are) and pooled
     samples (a pool's reads: those of its files, concatenated), the files still BAM files read whole, else the call fails -- opt-in
-    until its rate has been measured against the per-record path.  A `calling` backend is evaluated unit by unit either way."""
+    until its rate has been measured against the per-record path.  A `calling` backend is evaluated unit by unit either way.
+
+    estimate_frequencies = N: before a record is called, its prior allele frequencies are estimated by at most N iterations of
+    f' = sum_s K_s freqs_s(f) / sum_s K_s from the tag's values (or flat), freqs_s the mean posterior allele frequency of sample s
+    under prior (F_s, f) -- the reference's INFO/AFP fed back as --prior-frequencies --, ending early once max |f' - f| <
+    estimate_tolerance (estimate_prior_frequencies); the record is then called with the estimate as its prior frequencies and
+    carries INFO/EMIT, the iterations run.  Every sample needs an inbreeding value.  estimate_path: None = the likelihoods stay on
+    the device over the iterations where they fit and are formed again every iteration where not; "resident" / "recompute" force
+    one.  None (default): no estimate, no EMIT."""
     from .vcfheader import report_fields
 
     source = _source(sample_bams, base_error_rate, use_base_phred_scores, read_kw)
@@ -377,6 +606,9 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
     allele_filter = _allele_filter(vcf_path, filter_input_haplotypes)
     for block in _blocks(records, records_per_block):
         units = _exact_units(block, source, samples, prior_frequencies_tag, allele_filter, block_path)
+        if estimate_frequencies is not None:
+            estimate_prior_frequencies(units, samples, ploidy_of, inbreeding_of, estimate_frequencies, estimate_tolerance, calling,
+                                       estimate_path)
         results = _run_exact_groups(units, ploidy_of, inbreeding_of, full, calling)
         for ri, unit in enumerate(units):
             rec = unit["rec"]

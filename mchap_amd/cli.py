@@ -9,7 +9,9 @@ reference forks N processes over blocks of loci; here a block of loci is one GPU
 (`python -m torch.distributed.run --nproc-per-node N -m mchap_amd ...`, one rank per GPU) the targets / records are
 sharded over the ranks and rank 0 writes the one VCF; `--reference` may name a FASTA whose file is absent when its
 `.fai` index is present (contig lengths for the header; unknown reference bases are written as N); `--block-path
-{auto,off,on,wide}` chooses the host path of a block of targets / records (the block_path keyword of the programs)."""
+{auto,off,on,wide}` chooses the host path of a block of targets / records (the block_path keyword of the programs); `call-exact
+--estimate-prior-frequencies N [--estimate-tolerance EPS]` estimates every record's prior allele frequencies before it is called
+(application.estimate_prior_frequencies)."""
 import argparse
 import sys
 
@@ -126,6 +128,14 @@ def build_parser(program):
         _read_args(p)
         if program == "call":
             _mcmc_args(p)
+        else:
+            p.add_argument("--estimate-prior-frequencies", type=int, nargs=1, default=[None], metavar="N",
+                           help="(not a reference flag) estimate each record's prior allele frequencies before it is called: at most N "
+                                "rounds of the samples' posterior allele frequencies (INFO/AFP) fed back as the prior, from "
+                                "--prior-frequencies or flat; needs --use-dirmul-prior; the records carry INFO/EMIT")
+            p.add_argument("--estimate-tolerance", type=float, nargs=1, default=[None], metavar="EPS",
+                           help="(not a reference flag) with --estimate-prior-frequencies: stop a record once no frequency moves by "
+                                "EPS or more (default 1e-6)")
     p.add_argument("--report", type=str, nargs="*", default=[],
                    help="extra fields: AFPRIOR ACP AFP AOP AOPSUM GP GL SNVDP, optionally with an INFO/ or FORMAT/ prefix")
     p.add_argument("--cores", type=int, nargs=1, default=[1], help="host threads reading the alignment files")
@@ -215,9 +225,18 @@ def run(argv, out=None):
         inbreeding = io.sample_values(inb_arg, samples, float)
         contigs = io.vcf_contigs(args.haplotypes[0]) or (io.bam_header(next(iter(source.bams)))[0] if source.bams else [])
         if program == "call-exact":
+            estimate = args.estimate_prior_frequencies[0]
+            if estimate is None and args.estimate_tolerance[0] is not None:
+                raise ValueError("--estimate-tolerance needs --estimate-prior-frequencies")
+            if estimate is not None and estimate < 0:
+                raise ValueError("--estimate-prior-frequencies: N >= 0")
+            if estimate is not None and inbreeding is None:
+                raise ValueError("--estimate-prior-frequencies needs --use-dirmul-prior: the flat genotype prior has no allele "
+                                 "frequencies to estimate")
             records = application.call_exact(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
                                              inbreeding=inbreeding, filter_input_haplotypes=args.filter_input_haplotypes[0], shard=shard,
-                                             block_path=block_path)
+                                             block_path=block_path, estimate_frequencies=estimate,
+                                             estimate_tolerance=1e-6 if args.estimate_tolerance[0] is None else args.estimate_tolerance[0])
         else:
             seed = args.mcmc_seed[0]
             records = application.call(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
@@ -234,7 +253,8 @@ def run(argv, out=None):
         if rank != 0:
             return n_mine
         lines = [ln for part in gathered for ln in part]
-    for line in vcfheader.header_lines(program, ["mchap_amd"] + list(argv[1:]), samples, contigs, report=report, random_seed=seed):
+    for line in vcfheader.header_lines(program, ["mchap_amd"] + list(argv[1:]), samples, contigs, report=report, random_seed=seed,
+                                      estimate=program == "call-exact" and args.estimate_prior_frequencies[0] is not None):
         out.write(line + "\n")
     n = 0
     run.limit_records = 0

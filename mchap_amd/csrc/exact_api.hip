@@ -245,6 +245,83 @@ int mchap_exact_posterior_summaries_batch_device(int n_units, const double *post
   return launch_exact_array(A, n_units, reinterpret_cast<hipStream_t>(stream_));
 }
 
+// ---- prior allele frequencies by EM over stored likelihoods: one iteration = the counts launch per shape group, then the update
+// launch over the records ----
+int64_t mchap_exact_em_workspace_bytes(int n_units, int n_haps, int ploidy) {
+  if (n_units <= 0 || n_haps < 1 || ploidy < 1 || ploidy > MCHAP_MAX_PLOIDY_DENOVO) return 0;
+  if (!cwr_fits(n_haps, ploidy)) return -1;
+  return (int64_t)up256((size_t)n_units * (size_t)exact_nblk(host_cwr(n_haps, ploidy)) * ((size_t)n_haps + 2) * 8);
+}
+
+int mchap_exact_em_counts_device(int n_units, const double *llks64, int n_haps, int ploidy, const double *inbreeding,
+                                 const int32_t *unit_record, const int32_t *unit_slot, const double *frequencies, int stride,
+                                 const int32_t *record_active, double *slab, void *workspace, int64_t workspace_bytes, void *stream_) {
+  if (n_units <= 0) return MCHAP_OK;
+  if (!llks64 || !inbreeding || !unit_record || !unit_slot || !frequencies || !record_active || !slab)
+    return fail(MCHAP_ERR_BAD_ARG, "frequency estimate: NULL buffer");
+  if (ploidy < 1 || ploidy > MCHAP_MAX_PLOIDY_DENOVO) return fail(MCHAP_ERR_LIMIT, "ploidy %d not in 1..%d", ploidy, MCHAP_MAX_PLOIDY_DENOVO);
+  if (n_haps < 1 || stride < n_haps) return fail(MCHAP_ERR_BAD_ARG, "frequency estimate: rows of %d doubles for %d haplotypes", stride, n_haps);
+  if (!cwr_fits(n_haps, ploidy)) return fail(MCHAP_ERR_LIMIT, "ploidy %d over %d haplotypes: more than 2^62 genotypes", ploidy, n_haps);
+  const long long G = host_cwr(n_haps, ploidy);
+  const int nblk = exact_nblk(G);
+  if ((long long)n_units * nblk > 0x7fffffffll) return fail(MCHAP_ERR_LIMIT, "frequency estimate: %d units x %d tiles exceed one launch", n_units, nblk);
+  const int64_t need = mchap_exact_em_workspace_bytes(n_units, n_haps, ploidy);
+  if (!workspace || workspace_bytes < need)
+    return fail(MCHAP_ERR_BAD_ARG, "workspace of %lld bytes is too small: %lld needed (mchap_exact_em_workspace_bytes)", (long long)workspace_bytes,
+                (long long)need);
+  const size_t lds = mchap::exact_em_lds(n_haps, ploidy);
+  if (lds > 160 * 1024) return fail(MCHAP_ERR_LIMIT, "n_haps %d too large for the frequency estimate's prior tables", n_haps);
+  int rc = ensure_init();
+  if (rc) return rc;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  mchap::ExactEmParams E;
+  std::memset(&E, 0, sizeof(E));
+  E.llk64 = llks64;
+  E.inbreeding = inbreeding;
+  E.unit_record = unit_record;
+  E.unit_slot = unit_slot;
+  E.freqs = frequencies;
+  E.active = record_active;
+  E.stride = stride;
+  E.H = n_haps; E.K = ploidy; E.nblk = nblk;
+  E.G = G;
+  E.part = reinterpret_cast<double *>(workspace);
+  E.slab = slab;
+  auto k = ploidy <= 8 ? mchap::exact_em_counts_kernel<8> : mchap::exact_em_counts_kernel<mchap::EXACT_KMAX>;
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k, dim3((unsigned)((long long)n_units * nblk)), dim3(mchap::EXACT_THREADS), lds, stream, E);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(mchap::exact_em_combine_kernel, dim3(n_units), dim3(64), 0, stream, E);
+  HIP_TRY(hipGetLastError());
+  return MCHAP_OK;
+}
+
+int mchap_exact_em_update_device(int n_records, int n_samples, const int32_t *record_haps, int stride, const double *slab,
+                                 double ploidy_total, double tolerance, int max_iterations, double *frequencies,
+                                 int32_t *record_iterations, int32_t *record_active, double *record_delta, void *stream_) {
+  if (n_records <= 0) return MCHAP_OK;
+  if (!record_haps || !slab || !frequencies || !record_iterations || !record_active) return fail(MCHAP_ERR_BAD_ARG, "frequency update: NULL buffer");
+  if (n_samples < 1 || stride < 1 || !(ploidy_total > 0.0)) return fail(MCHAP_ERR_BAD_ARG, "frequency update: no samples");
+  int rc = ensure_init();
+  if (rc) return rc;
+  mchap::ExactEmUpdateParams U;
+  U.slab = slab;
+  U.record_haps = record_haps;
+  U.n_samples = n_samples;
+  U.stride = stride;
+  U.max_iterations = max_iterations;
+  U.ploidy_total = ploidy_total;
+  U.tolerance = tolerance;
+  U.freqs = frequencies;
+  U.iterations = record_iterations;
+  U.active = record_active;
+  U.delta = record_delta;
+  hipLaunchKernelGGL(mchap::exact_em_update_kernel, dim3(n_records), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_), U);
+  HIP_TRY(hipGetLastError());
+  return MCHAP_OK;
+}
+
 // ---- host-pointer forms: one device allocation, copies in, the device entry point, copies out ----
 int mchap_exact_genotype_likelihoods(const double *reads, int n_reads, int n_pos, int max_allele,
                                      const int64_t *read_counts, const int8_t *haplotypes, int n_haps, int ploidy,

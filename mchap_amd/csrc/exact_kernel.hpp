@@ -857,4 +857,219 @@ __global__ __launch_bounds__(EXACT_ARRAY_THREADS) void exact_array_kernel(const 
   }
 }
 
+// ---- prior allele frequencies by EM over stored likelihoods (application.estimate_prior_frequencies): one iteration is
+// f'[h] = sum_s K_s freqs_s(f)[h] / sum_s K_s over the samples s of a record, freqs_s the mean posterior allele frequency under
+// prior (F_s, f).  The likelihoods do not depend on f: pass 1 leaves them once in llk64 [U][G], and an iteration is a stream over
+// those doubles (exact_em_counts_kernel, exact_em_combine_kernel) and one small launch per record (exact_em_update_kernel). ----
+
+// The successor of an ascending genotype in VCF order: increment_genotype (jitutils.py:114-146) with constant indices, so that the
+// alleles stay in registers.
+template <int KM>
+__device__ __forceinline__ void next_genotype(int (&g)[KM], int K) {
+  int pos = K - 1;
+  bool found = false;
+#pragma unroll
+  for (int i = 1; i < KM; i++)
+    if (!found && i < K && g[i] != g[0]) {
+      pos = i - 1;
+      found = true;
+    }
+#pragma unroll
+  for (int i = 0; i < KM; i++) {
+    if (i == pos) g[i] += 1;
+    else if (i < pos) g[i] = 0;
+  }
+}
+
+struct ExactEmParams {
+  const double *llk64;         // [U][G] stored log likelihoods
+  const double *inbreeding;    // [U]
+  const int32_t *unit_record;  // [U] the unit's record within the sub-block
+  const int32_t *unit_slot;    // [U] the unit's row in the slab: (record, sample index)
+  const double *freqs;         // [records][stride] the records' current frequency rows
+  const int32_t *active;       // [records] 0: the record is frozen
+  int stride;                  // doubles per frequency row and per slab row (>= H)
+  int H, K, nblk;
+  long long G;
+  double *part;                // [U][nblk][H + 2]: block maximum of llk + log prior, sum and allele counts relative to it
+  double *slab;                // [slots][stride]: expected allele counts K_s * freqs_s of every (record, sample)
+};
+// a thread's run of consecutive genotypes, and the row pitch of the staging tile in doubles: 17 is odd, so the 32 lanes of a
+// half wavefront reading element j of their rows fall on 32 distinct bank pairs (ds_read_b64: bank = (byte / 4) % 64)
+constexpr int EXACT_EM_RUN = EXACT_GENOS_PER_BLOCK / EXACT_THREADS;
+constexpr int EXACT_EM_PITCH = EXACT_EM_RUN + 1;
+inline size_t exact_em_lds(int H, int K) {
+  return ((size_t)EXACT_THREADS * EXACT_EM_PITCH + (size_t)H * (K + 1) + (K + 1) + H + (size_t)(H + 1) * (EXACT_THREADS / 64) + 8) * 8;
+}
+// One workgroup per (unit, tile of 4096 genotypes).  The tile is loaded with consecutive lanes on consecutive genotypes (every
+// wavefront load is 512 contiguous bytes) into LDS; each thread then owns EXACT_EM_RUN consecutive genotypes: one unranking, then
+// the successor step.  The sums: a wavefront's 64 contributions by the shuffle reduction of pass 2 (wave_sum, fixed order), kept
+// per wavefront in LDS, wavefronts in order here, blocks in order in exact_em_combine_kernel.  No atomics.
+template <int KM = 8>
+__global__ __launch_bounds__(EXACT_THREADS) void exact_em_counts_kernel(const ExactEmParams P) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int unit = blockIdx.x / P.nblk, blk = blockIdx.x % P.nblk;
+  const int rec = P.unit_record[unit];
+  if (P.active[rec] == 0) return;  // (whole workgroup: the record is frozen, its slab rows stay)
+  const int H = P.H, K = P.K;
+  constexpr int NW = EXACT_THREADS / 64;
+  double *tile = reinterpret_cast<double *>(smem);       // [EXACT_THREADS][EXACT_EM_PITCH]
+  double *lgd = tile + EXACT_THREADS * EXACT_EM_PITCH;  // [H][K + 1]
+  double *lgf = lgd + (size_t)H * (K + 1);
+  double *lfreq = lgf + (K + 1);
+  double *acc = lfreq + H;                               // [NW][H + 1]
+  double *red = acc + (size_t)(H + 1) * NW;              // [NW] maxima, [1] left
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const double *fr = P.freqs + (size_t)rec * P.stride;
+  const double F = P.inbreeding[unit];
+  {
+    // the prior tables of exact_setup, from the unit's F and its record's current row
+    const double scale = (1.0 - F) / F;
+    for (int q = threadIdx.x; q < H * (K + 1); q += EXACT_THREADS) {
+      const int h = q / (K + 1), d = q % (K + 1);
+      const double alpha = fr[h] * scale;
+      lgd[q] = (F == 0.0 || d == 0) ? 0.0 : lgamma((double)d + alpha) - (lgamma((double)d + 1.0) + lgamma(alpha));
+    }
+    for (int d = threadIdx.x; d <= K; d += EXACT_THREADS) lgf[d] = lgamma((double)d + 1.0);
+    for (int h = threadIdx.x; h < H; h += EXACT_THREADS) lfreq[h] = fr[h];
+    if (threadIdx.x == 0) {
+      double sum_alpha = 0.0;
+      for (int h = 0; h < H; h++) sum_alpha += fr[h] * scale;
+      red[NW] = (F == 0.0) ? 0.0 : (lgamma((double)K + 1.0) + lgamma(sum_alpha)) - lgamma((double)K + sum_alpha);
+    }
+    for (int i = threadIdx.x; i < NW * (H + 1); i += EXACT_THREADS) acc[i] = 0.0;
+  }
+  const long long G = P.G;
+  const long long lo = (long long)blk * EXACT_GENOS_PER_BLOCK;
+  long long hi = lo + EXACT_GENOS_PER_BLOCK;
+  if (hi > G) hi = G;
+  const double *src = P.llk64 + (size_t)unit * G;
+#pragma unroll
+  for (int t = 0; t < EXACT_EM_RUN; t++) {
+    const int e = threadIdx.x + t * EXACT_THREADS;  // element of the tile: consecutive lanes, consecutive genotypes
+    if (lo + e < hi) tile[(e / EXACT_EM_RUN) * EXACT_EM_PITCH + (e % EXACT_EM_RUN)] = src[lo + e];
+  }
+  __syncthreads();
+  PriorTab pt;
+  pt.lgd = lgd;
+  pt.lgf = lgf;
+  pt.lfreq = lfreq;
+  pt.left = red[NW];
+  pt.lnH = log((double)H);
+  pt.F = F;
+  pt.has_freqs = 1;
+  // llk + log prior of the thread's run, and the block's maximum
+  const long long first = lo + (long long)threadIdx.x * EXACT_EM_RUN;
+  lds_cdouble *mine = lds_table(tile) + threadIdx.x * EXACT_EM_PITCH;
+  double lj[EXACT_EM_RUN];
+  double m = -INFINITY;
+  int g[KM], g0[KM];
+#pragma unroll
+  for (int k = 0; k < KM; k++) g[k] = 0;
+  if (first < hi) unrank_genotype(first, K, g);
+#pragma unroll
+  for (int k = 0; k < KM; k++) g0[k] = g[k];
+#pragma unroll
+  for (int t = 0; t < EXACT_EM_RUN; t++) {
+    lj[t] = -INFINITY;
+    if (first + t < hi) {
+      lj[t] = mine[t] + calling_log_prior(pt, g, K);
+      if (lj[t] > m) m = lj[t];
+      next_genotype(g, K);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o, WAVE));
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  m = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; w++) m = fmax(m, red[w]);
+  // second walk over the run: exp(lj - m) into the sum and the allele counts
+  double *wacc = acc + (size_t)wave * (H + 1);
+#pragma unroll
+  for (int k = 0; k < KM; k++) g[k] = g0[k];
+#pragma unroll
+  for (int t = 0; t < EXACT_EM_RUN; t++) {
+    const long long i0 = lo + (long long)(wave * 64) * EXACT_EM_RUN + t;  // the wavefront's first genotype of this step
+    if (i0 >= hi) continue;                                               // (wave-uniform)
+    const bool live = first + t < hi && lj[t] > -INFINITY;
+    const double p = live ? exp(lj[t] - m) : 0.0;
+    const double s = wave_sum(p);
+    if (lane == 0) wacc[H] += s;
+    for (int a = 0; a < H; a++) {
+      int cnt = 0;
+#pragma unroll
+      for (int k = 0; k < KM; k++) cnt += (k < K && g[k] == a) ? 1 : 0;
+      const double c = wave_sum(live ? p * (double)cnt : 0.0);
+      if (lane == 0) wacc[a] += c;
+    }
+    if (first + t < hi) next_genotype(g, K);
+  }
+  __syncthreads();
+  double *out = P.part + ((size_t)unit * P.nblk + blk) * (H + 2);
+  for (int h = threadIdx.x; h < H + 1; h += EXACT_THREADS) {
+    double sum = 0.0;
+    for (int w = 0; w < NW; w++) sum += acc[(size_t)w * (H + 1) + h];
+    out[h] = sum;
+  }
+  if (threadIdx.x == 0) out[H + 1] = m;
+}
+// The blocks of a unit in order: the normaliser, then the unit's expected allele counts into its slab row.
+static __global__ __launch_bounds__(64) void exact_em_combine_kernel(const ExactEmParams P) {
+  const int unit = blockIdx.x;
+  if (P.active[P.unit_record[unit]] == 0) return;
+  const int H = P.H;
+  const double *part = P.part + (size_t)unit * P.nblk * (H + 2);
+  double m = -INFINITY;
+  for (int q = 0; q < P.nblk; q++) m = fmax(m, part[(size_t)q * (H + 2) + H + 1]);
+  double total = 0.0;
+  for (int q = 0; q < P.nblk; q++) {
+    const double mq = part[(size_t)q * (H + 2) + H + 1];
+    if (mq > -INFINITY) total += part[(size_t)q * (H + 2) + H] * exp(mq - m);
+  }
+  for (int h = threadIdx.x; h < H; h += blockDim.x) {
+    double sum = 0.0;
+    for (int q = 0; q < P.nblk; q++) {
+      const double mq = part[(size_t)q * (H + 2) + H + 1];
+      if (mq > -INFINITY) sum += part[(size_t)q * (H + 2) + h] * exp(mq - m);
+    }
+    P.slab[(size_t)P.unit_slot[unit] * P.stride + h] = sum / total;
+  }
+}
+struct ExactEmUpdateParams {
+  const double *slab;         // [records][n_samples][stride]
+  const int32_t *record_haps; // [records] H of the record
+  int n_samples, stride, max_iterations;
+  double ploidy_total, tolerance;
+  double *freqs;              // [records][stride] in / out
+  int32_t *iterations;        // [records] in / out
+  int32_t *active;            // [records] in / out
+  double *delta;              // [records] max |f' - f| of the record's last iteration, or null
+};
+// One workgroup per record: the samples' rows in sample order, the new row, max |delta|, the iteration counter, and the freeze.
+static __global__ __launch_bounds__(64) void exact_em_update_kernel(const ExactEmUpdateParams P) {
+  const int rec = blockIdx.x;
+  if (P.active[rec] == 0) return;
+  const int H = P.record_haps[rec];
+  double *fr = P.freqs + (size_t)rec * P.stride;
+  const double *rows = P.slab + (size_t)rec * P.n_samples * P.stride;
+  double d = 0.0;
+  for (int h = threadIdx.x; h < H; h += blockDim.x) {
+    double sum = 0.0;
+    for (int s = 0; s < P.n_samples; s++) sum += rows[(size_t)s * P.stride + h];
+    const double f = sum / P.ploidy_total;
+    d = fmax(d, fabs(f - fr[h]));
+    fr[h] = f;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) d = fmax(d, __shfl_xor(d, o, WAVE));
+  if (threadIdx.x == 0) {
+    const int it = P.iterations[rec] + 1;
+    P.iterations[rec] = it;
+    if (P.delta) P.delta[rec] = d;
+    if (d < P.tolerance || it >= P.max_iterations) P.active[rec] = 0;
+  }
+}
+
 }  // namespace mchap

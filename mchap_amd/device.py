@@ -528,6 +528,33 @@ class ExactDeviceBatch:
             self._p(self.d_F), self._p(self.d_fr), C.byref(o), self._p(self.d_ws), C.c_int64(self.ws_bytes), C.c_void_p(stream))
         _lib.check(rc)
 
+    def _run_only(self, **outputs):
+        """mchap_exact_call_batch_device for the named outputs alone ({name: (elements, dtype)}), on torch's current stream."""
+        U, R, M, A, H, K = self.shape
+        o = _lib.ExactOut()
+        for nm, (n, dtype) in outputs.items():
+            setattr(o, nm, self._buf(nm, n, dtype).data_ptr())
+        stream = self.torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().mchap_exact_call_batch_device(
+            U, self._p(self.d_reads), R, M, A, self._p(self.d_counts), self._p(self.d_haps), H, K, self.has_prior,
+            self._p(self.d_F), self._p(self.d_fr), C.byref(o), self._p(self.d_ws), C.c_int64(self.ws_bytes), C.c_void_p(stream)))
+
+    def run_llks64(self):
+        """The unrounded float64 likelihoods [U * G] alone, left on the device (what the frequency estimate keeps resident)."""
+        self._run_only(llks64=(self.shape[0] * self.G, self.torch.float64))
+        return self.out["llks64"]
+
+    def run_freqs(self, frequencies=None):
+        """The mean posterior allele frequencies [U, H] alone (streaming form, both passes), under the prior frequencies
+        [U, H] given here in place of the batch's: one iteration of the frequency estimate's recompute path."""
+        U, R, M, A, H, K = self.shape
+        if frequencies is not None:
+            fr = self.torch.from_numpy(np.ascontiguousarray(frequencies, dtype=np.float64).reshape(-1))
+            assert self.d_fr is not None and fr.numel() == U * H
+            self.d_fr.copy_(fr)
+        self._run_only(freqs=(U * H, self.torch.float64))
+        return self._host("freqs", (U, H))
+
     def _host(self, name, shape):
         return self.out[name].cpu().numpy().reshape(shape)
 
@@ -546,6 +573,93 @@ class ExactDeviceBatch:
             res["llks"] = self._host("llks", (U, self.G))
             res["posteriors"] = self._host("posteriors", (U, self.G))
         return res
+
+
+class ExactFrequencyEstimate:
+    """Prior allele frequencies by EM for a sub-block of whole records whose likelihoods are resident on the device
+    (mchap_exact_em_counts_device, mchap_exact_em_update_device): the frequency rows, iteration counters and freeze flags of the
+    records live on the device; an iteration is one counts launch per group added and one update launch.
+
+    record_haps int [records]: haplotypes of each record; frequencies float64 [records, stride] (rows padded with 0): f_0;
+    n_samples: samples of every record; ploidy_total: the sum of their ploidies."""
+
+    def __init__(self, record_haps, frequencies, n_samples, ploidy_total, device=None):
+        torch = _torch()
+        self.torch = torch
+        self.device = dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        fr = np.ascontiguousarray(frequencies, dtype=np.float64)
+        self.n_records, self.stride = fr.shape
+        self.n_samples, self.ploidy_total = int(n_samples), float(ploidy_total)
+        haps = np.ascontiguousarray(record_haps, dtype=np.int32)
+        assert haps.shape == (self.n_records,) and haps.min() >= 1 and haps.max() <= self.stride
+        self.d_haps = torch.from_numpy(haps).to(dev)
+        self.d_freqs = torch.from_numpy(fr.reshape(-1).copy()).to(dev)
+        self.d_iters = torch.zeros(self.n_records, dtype=torch.int32, device=dev)
+        self.d_active = torch.ones(self.n_records, dtype=torch.int32, device=dev)
+        self.d_delta = torch.zeros(self.n_records, dtype=torch.float64, device=dev)
+        self.d_slab = torch.zeros(self.n_records * self.n_samples * self.stride, dtype=torch.float64, device=dev)
+        self.groups = []
+        self.launches = 0   # iterations enqueued
+
+    def add_group(self, llks64, n_haps, ploidy, inbreeding, unit_record, unit_sample):
+        """The units of one shape (n_haps, ploidy): llks64 a float64 torch tensor [U * G] on the device (kept, not copied);
+        inbreeding [U]; unit_record / unit_sample [U]: the record of the sub-block and the sample index of each unit."""
+        torch, dev = self.torch, self.device
+        from math import comb
+
+        rec = np.ascontiguousarray(unit_record, dtype=np.int32)
+        smp = np.ascontiguousarray(unit_sample, dtype=np.int32)
+        U = len(rec)
+        G = comb(int(n_haps) + int(ploidy) - 1, int(ploidy))
+        assert llks64.dtype == torch.float64 and llks64.numel() == U * G and llks64.is_contiguous()
+        assert U == 0 or (rec.min() >= 0 and rec.max() < self.n_records and smp.min() >= 0 and smp.max() < self.n_samples)
+        assert int(n_haps) <= self.stride
+        wsb = int(_lib.lib().mchap_exact_em_workspace_bytes(U, int(n_haps), int(ploidy)))
+        if wsb < 0:
+            raise NotImplementedError("mchap_hip: ploidy %d over %d haplotypes: more than 2^62 genotypes" % (int(ploidy), int(n_haps)))
+        self.groups.append(dict(
+            U=U, H=int(n_haps), K=int(ploidy), llks=llks64, wsb=wsb,
+            F=torch.from_numpy(np.array(np.broadcast_to(np.asarray(inbreeding, dtype=np.float64), (U,)))).to(dev),
+            rec=torch.from_numpy(rec).to(dev), slot=torch.from_numpy(rec * np.int32(self.n_samples) + smp).to(dev),
+            ws=torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)))
+
+    def freeze(self, records):
+        """Records that take no part (a group of theirs was refused): frozen from the start."""
+        if len(records):
+            self.d_active[self.torch.from_numpy(np.ascontiguousarray(records, dtype=np.int64)).to(self.device)] = 0
+
+    def step(self, tolerance, max_iterations):
+        """One iteration, enqueued on torch's current stream: the counts launches, then the update launch."""
+        L = _lib.lib()
+        p = lambda t: C.c_void_p(t.data_ptr())
+        stream = C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+        for g in self.groups:
+            _lib.check(L.mchap_exact_em_counts_device(g["U"], p(g["llks"]), g["H"], g["K"], p(g["F"]), p(g["rec"]), p(g["slot"]),
+                                                      p(self.d_freqs), self.stride, p(self.d_active), p(self.d_slab), p(g["ws"]),
+                                                      C.c_int64(g["wsb"]), stream))
+        _lib.check(L.mchap_exact_em_update_device(self.n_records, self.n_samples, p(self.d_haps), self.stride, p(self.d_slab),
+                                                  C.c_double(self.ploidy_total), C.c_double(float(tolerance)), int(max_iterations),
+                                                  p(self.d_freqs), p(self.d_iters), p(self.d_active), p(self.d_delta), stream))
+        self.launches += 1
+
+    def n_active(self):
+        return int(self.d_active.sum().item())
+
+    def run(self, max_iterations, tolerance, poll=4):
+        """Iterations until every record is frozen: at most max_iterations launches, the number of active records read back every
+        `poll` iterations only to stop launching early (a frozen record's units exit at once, so the result does not depend on it)."""
+        if int(max_iterations) <= 0:
+            return
+        done = 0
+        while done < int(max_iterations):
+            self.step(tolerance, max_iterations)
+            done += 1
+            if done % max(1, int(poll)) == 0 and done < int(max_iterations) and self.n_active() == 0:
+                break
+
+    def results(self):
+        """(frequencies [records, stride], iterations [records]) on the host."""
+        return (self.d_freqs.cpu().numpy().reshape(self.n_records, self.stride), self.d_iters.cpu().numpy().astype(np.int64))
 
 
 class DenovoRaggedBatch(_OwnBuffers):

@@ -128,6 +128,8 @@ def _format_exact_record(unit, samples, results, ri, ploidy_of, report, prior_ta
                 parts.append(k)
         else:
             parts.append("%s=%s" % (k, vcfstr(np.asarray(v) if isinstance(v, np.ndarray) else v)))
+    if "emit" in unit:   # (call-exact --estimate-prior-frequencies: the iterations run for the record, null where none was)
+        parts.append("EMIT=%s" % ("." if unit["emit"] is None or invalid else unit["emit"]))
     fmt = ":".join(SAMPLE_FIELDS + tuple(fmt_opt))
     return invalid or "PASS", ";".join(parts), fmt, cols
 

@@ -80,8 +80,13 @@ def report_fields(report):
     return info, fmt
 
 
-def header_lines(program, command, samples, contigs, report=(), random_seed=None, today=None, version=None):
-    """The header block as a list of lines.  contigs: [(name, length)]; command: the argv list or a string."""
+# call-exact --estimate-prior-frequencies (not a reference field): declared only with the flag
+EMIT_INFO_FIELD = ("EMIT", "1", "Integer", "Iterations of the prior allele-frequency estimate run for the record")
+
+
+def header_lines(program, command, samples, contigs, report=(), random_seed=None, today=None, version=None, estimate=False):
+    """The header block as a list of lines.  contigs: [(name, length)]; command: the argv list or a string.  estimate: the records
+    carry INFO/EMIT (call-exact --estimate-prior-frequencies)."""
     from . import __version__
 
     d = today or date.today()
@@ -96,6 +101,8 @@ def header_lines(program, command, samples, contigs, report=(), random_seed=None
         out.append('##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % (fid, num, typ, descr))
     for fid in info_opt:
         out.append('##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % ((fid,) + OPTIONAL_INFO_FIELDS[fid]))
+    if estimate:
+        out.append('##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % EMIT_INFO_FIELD)
     for fid, num, typ, descr in FORMAT_FIELDS:
         out.append('##FORMAT=<ID=%s,Number=%s,Type=%s,Description="%s">' % (fid, num, typ, descr))
     for fid in fmt_opt:
