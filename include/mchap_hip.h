@@ -358,6 +358,8 @@ int mchap_exact_em_counts_device(int n_units, const double *llks64, int n_haps, 
  * and divided by ploidy_total = sum_s K_s into its row of `frequencies` (record_haps [records]: its number of haplotypes, at most
  * stride), max |f' - f| into record_delta (or NULL), record_iterations + 1, and record_active = 0 once the maximum is below
  * `tolerance` or the counter has reached max_iterations: the host only counts the active records now and then to stop launching.
+ * A NaN in the new row (a sample of the record without a finite genotype) makes the maximum NaN, and NaN is not below `tolerance`:
+ * such a record runs max_iterations and keeps its NaN row, as the host's definition does.
  * Enqueues on `stream`, no synchronisation. */
 int mchap_exact_em_update_device(int n_records, int n_samples, const int32_t *record_haps, int stride, const double *slab,
                                  double ploidy_total, double tolerance, int max_iterations, double *frequencies,

@@ -1047,7 +1047,11 @@ struct ExactEmUpdateParams {
   int32_t *active;            // [records] in / out
   double *delta;              // [records] max |f' - f| of the record's last iteration, or null
 };
+// the larger of two |delta|, a NaN on either side kept (fmax would drop it)
+__device__ __forceinline__ double em_delta_max(double d, double e) { return (e > d || e != e) ? e : d; }
 // One workgroup per record: the samples' rows in sample order, the new row, max |delta|, the iteration counter, and the freeze.
+// A NaN in the new row (a sample without a finite genotype: 0 / 0) makes max |delta| NaN, and NaN does not meet the tolerance, as
+// application._em_update's `max |f' - f| < eps` is False for it: such a record runs max_iterations and keeps its NaN row.
 static __global__ __launch_bounds__(64) void exact_em_update_kernel(const ExactEmUpdateParams P) {
   const int rec = blockIdx.x;
   if (P.active[rec] == 0) return;
@@ -1059,11 +1063,11 @@ static __global__ __launch_bounds__(64) void exact_em_update_kernel(const ExactE
     double sum = 0.0;
     for (int s = 0; s < P.n_samples; s++) sum += rows[(size_t)s * P.stride + h];
     const double f = sum / P.ploidy_total;
-    d = fmax(d, fabs(f - fr[h]));
+    d = em_delta_max(d, fabs(f - fr[h]));
     fr[h] = f;
   }
 #pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) d = fmax(d, __shfl_xor(d, o, WAVE));
+  for (int o = 32; o >= 1; o >>= 1) d = em_delta_max(d, __shfl_xor(d, o, WAVE));
   if (threadIdx.x == 0) {
     const int it = P.iterations[rec] + 1;
     P.iterations[rec] = it;
