@@ -3,6 +3,7 @@ torch stream through the `*_device` entry points of the C ABI.  torch is used fo
 streams and (in bench.py) torch.distributed only.
 """
 import ctypes as C
+from math import comb
 
 import numpy as np
 
@@ -16,6 +17,16 @@ def _torch():
     if not torch.cuda.is_available():
         raise _lib.MchapLibraryError("no MI355X visible to torch: the device path needs a GPU (no CPU fallback)")
     return torch
+
+
+def _ptr(t):
+    """Torch tensor `t` as the C ABI takes a device buffer (None: NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _device(torch, device):
+    """`device`, by default torch's current GPU."""
+    return torch.device("cuda", torch.cuda.current_device()) if device is None else device
 
 
 def pinned(a):
@@ -64,9 +75,14 @@ class _OwnBuffers:
     """A device batch owns its buffers (inputs, workspace, traces, summaries): two passes over it must not overlap, whatever
     streams they are issued on.  Every enqueueing method waits for the event the previous one left behind and leaves its
     own -- passes of ONE batch are serialised on the device, passes of different batches still run side by side
-    (PassesInFlight)."""
+    (PassesInFlight).
+
+    The base of the de novo batches also sets those buffers up and launches the sampler over them: a batch builds its unit
+    descriptors and input tensors (d_reads, or the compact input through _upload_compact), then _allocate; _fit is the launch."""
 
     _last_use = None
+    _two_words = True   # the batch takes units of two trace words per haplotype (the general sampler's)
+    d_reads = d_calls = d_quals = d_qual_prob = None
 
     def _begin(self):
         s = self.torch.cuda.current_stream()
@@ -79,11 +95,74 @@ class _OwnBuffers:
         ev.record(self.torch.cuda.current_stream())
         self._last_use = ev
 
+    def _allocate(self, desc, trace_words, llks, fixed):
+        """Descriptors `desc` (their trace_off in words of a one-word batch) to the device, the outputs -- trace_words int64 (times
+        the words per haplotype), llks float64, fixed int8, a status per unit -- and the workspace; sets cfg from self.max_pos."""
+        torch, dev, L = self.torch, self.device, _lib.lib()
+        U = len(desc)
+        self.units_host, self.n_units = desc, U
+        self.cfg = self.model._cfg(self.max_pos)
+        # uint64 words per haplotype of the traces: 2 when the batch holds a unit of more than 62 SNVs / 64 bits per haplotype
+        self.wph = int(L.mchap_denovo_trace_words_per_haplotype(C.byref(self.cfg), U, _lib.ptr(desc)))
+        if self.wph < 1:
+            raise NotImplementedError("mchap_hip: unsupported unit shape (" + _lib.last_error() + ")")
+        if self.wph > 1 and not self._two_words:
+            raise NotImplementedError("DenovoDeviceBatch holds one trace word per haplotype: units wider than 62 SNVs / 64 bits go "
+                                      "through DenovoMCMC.fit_batch or DenovoRaggedBatch")
+        desc["trace_off"] *= self.wph
+        self.d_units = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(dev)
+        self.d_trace = torch.empty(int(trace_words) * self.wph, dtype=torch.int64, device=dev)
+        self.d_llks = torch.empty(int(llks), dtype=torch.float64, device=dev)
+        self.d_fixed = torch.empty(int(fixed), dtype=torch.int8, device=dev)
+        self.d_status = torch.empty(U, dtype=torch.int32, device=dev)
+        self.ws_bytes = int(L.mchap_denovo_workspace_bytes(C.byref(self.cfg), U, _lib.ptr(desc)))
+        if self.ws_bytes < 0:
+            raise NotImplementedError("mchap_hip: unsupported unit shape")
+        self.d_ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=dev)
+
+    def _upload_compact(self, calls, quals, error_rate, non_blocking=False, reject_negative=None):
+        """The compact input in place of d_reads: int8 calls (< 0 = gap), optional int16 quals of the same shape, and the table
+        a called cell's quality is looked up in (one entry without qualities).  reject_negative: the name under which a called
+        cell of negative quality is refused."""
+        from .blockpath import qual_prob_table
+
+        torch, dev = self.torch, self.device
+        calls = np.ascontiguousarray(calls, dtype=np.int8)
+        self.d_reads = None
+        self.d_calls = torch.from_numpy(calls.reshape(-1)).to(dev, non_blocking=non_blocking)
+        table = np.array([1.0 - error_rate], dtype=np.float64)   # qualities ignored: every called cell's probability
+        if quals is not None:
+            quals = np.ascontiguousarray(quals, dtype=np.int16)
+            assert quals.shape == calls.shape
+            if reject_negative and (quals[calls >= 0] < 0).any():
+                raise AssertionError(reject_negative + ": a called cell has a negative quality")
+            self.d_quals = torch.from_numpy(quals.reshape(-1)).to(dev, non_blocking=non_blocking)
+            table = qual_prob_table(error_rate, int(quals.max(initial=0)) + 1)   # reference io/bam.py:280-288
+        self.qual_prob_len = len(table)
+        self.d_qual_prob = torch.from_numpy(table).to(dev)
+
+    def _fit(self, stream):
+        """The sampler launch on `stream` (a raw hipStream_t): from the float64 read tensors, or -- d_reads is None -- from the
+        compact input, the tensors formed on the device by the prepare pass (mchap_denovo_fit_batch_calls_device)."""
+        L = _lib.lib()
+        self.cfg.cache_epoch = _lib.next_cache_epoch()  # (the call's own: one sequence for every library copy of the process)
+        head = (C.byref(self.cfg), self.n_units, _ptr(self.d_units), _lib.ptr(self.units_host))
+        tail = (_ptr(self.d_counts), _ptr(self.d_nalleles), None, _ptr(self.d_trace), _ptr(self.d_llks), _ptr(self.d_fixed),
+                _ptr(self.d_status), _ptr(self.d_ws), C.c_int64(self.ws_bytes), C.c_void_p(stream))
+        if self.d_reads is None:
+            rc = L.mchap_denovo_fit_batch_calls_device(*head, _ptr(self.d_calls), _ptr(self.d_quals), _ptr(self.d_qual_prob),
+                                                       int(self.qual_prob_len), *tail)
+        else:
+            rc = L.mchap_denovo_fit_batch_device(*head, _ptr(self.d_reads), *tail)
+        _lib.check(rc)
+
 
 class DenovoDeviceBatch(_OwnBuffers):
     """A batch of uniformly shaped units resident on one GPU.
 
     reads : float64 [U, R, M, A] (numpy, copied once) ; read_counts : int64 [U, R] or None."""
+
+    _two_words = False   # (posterior / traces hold one word per haplotype)
 
     def __init__(self, model: DenovoMCMC, reads, read_counts=None, first_stream=0, device=None, calls=None, quals=None,
                  error_rate=0.0024):
@@ -95,13 +174,11 @@ class DenovoDeviceBatch(_OwnBuffers):
         torch = _torch()
         self.torch = torch
         self.model = model
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        self.d_calls = self.d_quals = self.d_qual_prob = None
+        self.device = _device(torch, device)
         if reads is None:
             calls = np.ascontiguousarray(calls, dtype=np.int8)
             U, R, M = calls.shape
             A = int(np.max(model.n_alleles))
-            reads = None
         else:
             reads = np.ascontiguousarray(reads, dtype=np.float64)
             U, R, M, A = reads.shape
@@ -120,40 +197,16 @@ class DenovoDeviceBatch(_OwnBuffers):
         units["n_reads"], units["n_pos"], units["max_allele"], units["ploidy"] = R, M, A, K
         units["inbreeding"] = np.nan if model.inbreeding is None else float(model.inbreeding)
         units["stream_id"] = (first_stream + idx).astype(np.uint64)
-        self.units_host = units
         dev = self.device
-        self.d_units = torch.from_numpy(units.view(np.uint8).reshape(-1)).to(dev)
         if reads is not None:
             self.d_reads = torch.from_numpy(reads.reshape(-1)).to(dev, non_blocking=True)
         else:
-            from .encoding import prob_of_qual
-
-            self.d_reads = None
-            self.d_calls = torch.from_numpy(calls.reshape(-1)).to(dev, non_blocking=True)
-            if quals is not None:
-                quals = np.ascontiguousarray(quals, dtype=np.int16)
-                assert quals.shape == calls.shape
-                self.d_quals = torch.from_numpy(quals.reshape(-1)).to(dev, non_blocking=True)
-                table = prob_of_qual(np.arange(int(quals.max(initial=0)) + 1)) * (1.0 - error_rate)  # reference io/bam.py:280-288
-            else:
-                table = np.array([1.0 - error_rate])
-            self.qual_prob_len = len(table)
-            self.d_qual_prob = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(dev)
+            # (unlike DenovoRaggedBatch.from_calls, a called cell of negative quality is not refused here)
+            self._upload_compact(calls, quals, error_rate, non_blocking=True)
         self.d_counts = None if read_counts is None else torch.from_numpy(np.ascontiguousarray(read_counts, dtype=np.int64).reshape(-1)).to(dev)
         self.d_nalleles = torch.from_numpy(np.asarray(model.n_alleles, dtype=np.int8)).to(dev)
-        self.d_trace = torch.empty(U * Cn * S * K, dtype=torch.int64, device=dev)
-        self.d_llks = torch.empty(U * Cn * S, dtype=torch.float64, device=dev)
-        self.d_fixed = torch.empty(U * M, dtype=torch.int8, device=dev)
-        self.d_status = torch.empty(U, dtype=torch.int32, device=dev)
-        self.cfg = model._cfg(M)
-        L = _lib.lib()
-        self.ws_bytes = int(L.mchap_denovo_workspace_bytes(C.byref(self.cfg), U, _lib.ptr(units)))
-        if self.ws_bytes < 0:
-            raise NotImplementedError("mchap_hip: unsupported unit shape")
-        if int(L.mchap_denovo_trace_words_per_haplotype(C.byref(self.cfg), U, _lib.ptr(units))) != 1:
-            raise NotImplementedError("DenovoDeviceBatch holds one trace word per haplotype: units wider than 62 SNVs / 64 bits go "
-                                      "through DenovoMCMC.fit_batch or DenovoRaggedBatch")
-        self.d_ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=dev)
+        self.max_pos = M
+        self._allocate(units, U * Cn * S * K, U * Cn * S, U * M)
         self.post = None
         self.sampler_name = _lib.sampler_name(self.cfg, units)
         self.timer = None
@@ -167,28 +220,9 @@ class DenovoDeviceBatch(_OwnBuffers):
     def sampler_ms(self):
         return -1.0 if self.timer is None else self.timer.ms()
 
-    def _p(self, t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-
     def run(self):
         """Enqueue the sampler on torch's current stream (no synchronisation)."""
-        L = _lib.lib()
-        stream = self._begin().cuda_stream
-        self.cfg.cache_epoch = _lib.next_cache_epoch()  # (the call's own: one sequence for every library copy of the process)
-        if self.d_reads is None:
-            rc = L.mchap_denovo_fit_batch_calls_device(
-                C.byref(self.cfg), self.shape[0], self._p(self.d_units), _lib.ptr(self.units_host), self._p(self.d_calls),
-                self._p(self.d_quals), self._p(self.d_qual_prob), int(self.qual_prob_len), self._p(self.d_counts),
-                self._p(self.d_nalleles), None, self._p(self.d_trace), self._p(self.d_llks), self._p(self.d_fixed),
-                self._p(self.d_status), self._p(self.d_ws), C.c_int64(self.ws_bytes), C.c_void_p(stream))
-            _lib.check(rc)
-            self._end()
-            return
-        rc = L.mchap_denovo_fit_batch_device(
-            C.byref(self.cfg), self.shape[0], self._p(self.d_units), _lib.ptr(self.units_host), self._p(self.d_reads),
-            self._p(self.d_counts), self._p(self.d_nalleles), None, self._p(self.d_trace), self._p(self.d_llks),
-            self._p(self.d_fixed), self._p(self.d_status), self._p(self.d_ws), C.c_int64(self.ws_bytes), C.c_void_p(stream))
-        _lib.check(rc)
+        self._fit(self._begin().cuda_stream)
         self._end()
 
     def posterior(self, burn, max_states=32):
@@ -210,9 +244,9 @@ class DenovoDeviceBatch(_OwnBuffers):
         P = self.post
         stream = self._begin().cuda_stream
         rc = _lib.lib().mchap_trace_posterior_batch_device(
-            U, self._p(self.d_units), self.S, self.Cn, int(burn), self._p(self.d_trace), int(max_states), self.K,
-            self._p(P["words"]), self._p(P["counts"]), self._p(P["n"]), self._p(P["stats"]), self._p(P["mode"]),
-            self._p(P["mode_words"]), self._p(P["mode_count"]), C.c_void_p(stream))
+            U, _ptr(self.d_units), self.S, self.Cn, int(burn), _ptr(self.d_trace), int(max_states), self.K,
+            _ptr(P["words"]), _ptr(P["counts"]), _ptr(P["n"]), _ptr(P["stats"]), _ptr(P["mode"]),
+            _ptr(P["mode_words"]), _ptr(P["mode_count"]), C.c_void_p(stream))
         _lib.check(rc)
         self._end()
 
@@ -225,8 +259,8 @@ class DenovoDeviceBatch(_OwnBuffers):
             self.d_mci = torch.empty(U, dtype=torch.int32, device=self.device)
         stream = self._begin().cuda_stream
         rc = _lib.lib().mchap_trace_incongruence_batch_device(
-            U, self._p(self.d_units), self.S, self.Cn, int(burn), self._p(self.d_trace), self.K, C.c_double(float(threshold)),
-            self._p(self.d_mci), C.c_void_p(stream))
+            U, _ptr(self.d_units), self.S, self.Cn, int(burn), _ptr(self.d_trace), self.K, C.c_double(float(threshold)),
+            _ptr(self.d_mci), C.c_void_p(stream))
         _lib.check(rc)
         self._end()
         return self.d_mci
@@ -273,35 +307,7 @@ def call_reads_from_calls(calls, counts, unit_rows, unit_call_off, unit_count_of
     unit [U], the two offset arrays [U], n_alleles int8 [U, M].  Uploads them and enqueues the fill on torch's current stream (no
     synchronisation).  Returns (reads float64 [U, n_reads, M, max_allele], read_counts int64 [U, n_reads]) as torch tensors:
     encoding.encode_read_distributions of every unit's rows without qualities, padded to n_reads with NaN rows of count 0."""
-    torch = _torch()
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    calls = np.ascontiguousarray(calls, dtype=np.int8).reshape(-1)
-    counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
-    rows = np.ascontiguousarray(unit_rows, dtype=np.int64)
-    c_off = np.ascontiguousarray(unit_call_off, dtype=np.int64)
-    n_off = np.ascontiguousarray(unit_count_off, dtype=np.int64)
-    nal = np.ascontiguousarray(n_alleles, dtype=np.int8)
-    U, M = nal.shape
-    R, A = int(n_reads), int(max_allele)
-    if not (rows.shape == c_off.shape == n_off.shape == (U,)) or R < 1 or M < 1 or A < 1:
-        raise AssertionError("call_reads_from_calls: per-unit arrays of one length, n_reads, positions and max_allele at least 1")
-    # (the kernel reads calls / counts at these offsets: checked here, where the arrays are still on the host)
-    if U and (rows.min() < 0 or rows.max() > R or c_off.min() < 0 or n_off.min() < 0 or (c_off + rows * M).max() > len(calls)
-              or (n_off + rows).max() > len(counts)):
-        raise AssertionError("call_reads_from_calls: a unit's rows lie outside calls / counts, or exceed n_reads")
-    up = lambda a: torch.from_numpy(a).to(dev) if a.size else None  # noqa: E731
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-    d_in = [up(a) for a in (calls, counts, rows, c_off, n_off, nal.reshape(-1))]
-    d_reads = torch.empty((U, R, M, A), dtype=torch.float64, device=dev)
-    d_counts = torch.empty((U, R), dtype=torch.int64, device=dev)
-    p_call = 1.0 - error_rate             # (as encoding.encode_read_distributions / as_probabilistic form them)
-    p_other = (1.0 - p_call) / 3.0
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().mchap_call_reads_from_calls_device(
-            U, *[p(t) for t in d_in], R, M, A, C.c_double(p_call), C.c_double(p_other), p(d_reads), p(d_counts), C.c_void_p(stream)))
-    # (the inputs were allocated and are consumed on this stream: the allocator reuses them only for later work of the same stream)
-    return d_reads, d_counts
+    return _call_reads(calls, counts, unit_rows, unit_call_off, unit_count_off, n_alleles, n_reads, max_allele, error_rate, device)
 
 
 def call_reads_from_calls_quals(calls, quals, counts, unit_rows, unit_call_off, unit_count_off, n_alleles, n_reads, max_allele,
@@ -311,12 +317,19 @@ def call_reads_from_calls_quals(calls, quals, counts, unit_rows, unit_call_off, 
     encoding.encode_read_distributions / as_probabilistic form them -- hold n_qual entries: by default one more than the largest
     quality of a called cell of the units.  Returns the same pair of torch tensors: encoding.encode_read_distributions of every
     unit's rows with their qualities, padded to n_reads with NaN rows of count 0."""
+    return _call_reads(calls, counts, unit_rows, unit_call_off, unit_count_off, n_alleles, n_reads, max_allele, error_rate, device,
+                       quals=quals, n_qual=n_qual)
+
+
+def _call_reads(calls, counts, unit_rows, unit_call_off, unit_count_off, n_alleles, n_reads, max_allele, error_rate, device,
+                quals=None, n_qual=None):
+    """call_reads_from_calls, or with `quals` call_reads_from_calls_quals: the host-side checks, the upload and the fill."""
     from .blockpath import _ragged_arange, qual_prob_table
 
+    name = "call_reads_from_calls" if quals is None else "call_reads_from_calls_quals"
     torch = _torch()
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    dev = _device(torch, device)
     calls = np.ascontiguousarray(calls, dtype=np.int8).reshape(-1)
-    quals = np.ascontiguousarray(quals, dtype=np.int16).reshape(-1)
     counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
     rows = np.ascontiguousarray(unit_rows, dtype=np.int64)
     c_off = np.ascontiguousarray(unit_call_off, dtype=np.int64)
@@ -324,32 +337,42 @@ def call_reads_from_calls_quals(calls, quals, counts, unit_rows, unit_call_off, 
     nal = np.ascontiguousarray(n_alleles, dtype=np.int8)
     U, M = nal.shape
     R, A = int(n_reads), int(max_allele)
-    if not (rows.shape == c_off.shape == n_off.shape == (U,)) or R < 1 or M < 1 or A < 1 or len(quals) != len(calls):
-        raise AssertionError("call_reads_from_calls_quals: per-unit arrays of one length, as many qualities as calls, n_reads, positions "
-                             "and max_allele at least 1")
+    host = [calls, counts, rows, c_off, n_off, nal.reshape(-1)]
+    if quals is not None:
+        quals = np.ascontiguousarray(quals, dtype=np.int16).reshape(-1)
+        host.insert(1, quals)
+    if not (rows.shape == c_off.shape == n_off.shape == (U,)) or R < 1 or M < 1 or A < 1 or (quals is not None and len(quals) != len(calls)):
+        raise AssertionError("%s: per-unit arrays of one length, %sn_reads, positions and max_allele at least 1"
+                             % (name, "" if quals is None else "as many qualities as calls, "))
     # (the kernel reads calls / quals / counts at these offsets: checked here, where the arrays are still on the host)
     if U and (rows.min() < 0 or rows.max() > R or c_off.min() < 0 or n_off.min() < 0 or (c_off + rows * M).max() > len(calls)
               or (n_off + rows).max() > len(counts)):
-        raise AssertionError("call_reads_from_calls_quals: a unit's rows lie outside calls / counts, or exceed n_reads")
-    # ... and the tables at the qualities of the units' called cells
-    owner, k = _ragged_arange(rows * M)
-    used = c_off[owner] + k
-    q_called = quals[used][calls[used] >= 0]
-    n_qual = int(q_called.max(initial=0)) + 1 if n_qual is None else int(n_qual)
-    if n_qual < 1 or (len(q_called) and (q_called.min() < 0 or q_called.max() >= n_qual)):
-        raise AssertionError("call_reads_from_calls_quals: the quality of a called cell lies outside the table (0 <= q < %d)" % n_qual)
-    p_call = qual_prob_table(error_rate, n_qual)     # (as encoding.encode_read_distributions / as_probabilistic form them)
-    p_other = (1.0 - p_call) / 3.0
+        raise AssertionError("%s: a unit's rows lie outside calls / counts, or exceed n_reads" % name)
     up = lambda a: torch.from_numpy(a).to(dev) if a.size else None  # noqa: E731
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-    d_in = [up(a) for a in (calls, quals, counts, rows, c_off, n_off, nal.reshape(-1))]
-    d_tab = [up(np.ascontiguousarray(p_call)), up(np.ascontiguousarray(p_other))]
+    # the probability of a called cell's allele and of each other allele, as encoding.encode_read_distributions / as_probabilistic
+    # form them: two numbers, or with qualities two tables
+    if quals is None:
+        fill = _lib.lib().mchap_call_reads_from_calls_device
+        p_call = 1.0 - error_rate
+        d_tab, probs = [], (C.c_double(p_call), C.c_double((1.0 - p_call) / 3.0))
+    else:
+        fill = _lib.lib().mchap_call_reads_from_calls_quals_device
+        # ... which the kernel reads at the qualities of the units' called cells
+        owner, k = _ragged_arange(rows * M)
+        used = c_off[owner] + k
+        q_called = quals[used][calls[used] >= 0]
+        n_qual = int(q_called.max(initial=0)) + 1 if n_qual is None else int(n_qual)
+        if n_qual < 1 or (len(q_called) and (q_called.min() < 0 or q_called.max() >= n_qual)):
+            raise AssertionError("%s: the quality of a called cell lies outside the table (0 <= q < %d)" % (name, n_qual))
+        p_call = qual_prob_table(error_rate, n_qual)
+        d_tab = [up(np.ascontiguousarray(p_call)), up(np.ascontiguousarray((1.0 - p_call) / 3.0))]
+        probs = (_ptr(d_tab[0]), _ptr(d_tab[1]), n_qual)
+    d_in = [up(a) for a in host]
     d_reads = torch.empty((U, R, M, A), dtype=torch.float64, device=dev)
     d_counts = torch.empty((U, R), dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_lib.lib().mchap_call_reads_from_calls_quals_device(
-            U, *[p(t) for t in d_in], R, M, A, p(d_tab[0]), p(d_tab[1]), n_qual, p(d_reads), p(d_counts), C.c_void_p(stream)))
+        _lib.check(fill(U, *[_ptr(t) for t in d_in], R, M, A, *probs, _ptr(d_reads), _ptr(d_counts), C.c_void_p(stream)))
     # (the inputs were allocated and are consumed on this stream: the allocator reuses them only for later work of the same stream)
     return d_reads, d_counts
 
@@ -374,6 +397,7 @@ class CompactCallReads:
 
     def on_device(self, device=None):
         """(reads, read_counts) device tensors, the fill enqueued on torch's current stream."""
+        # (through the public names: the tests count the fills by wrapping them)
         if self.quals is not None:
             return call_reads_from_calls_quals(self.compact[0], self.quals, *self.compact[1:], self.n_reads, self.max_allele,
                                                error_rate=self.error_rate, device=device)
@@ -426,7 +450,7 @@ class ExactDeviceBatch:
 
     def __init__(self, reads, ploidy, haplotypes, read_counts=None, prior=None, device=None, cache_joint=True):
         torch = _torch()
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        dev = _device(torch, device)
         reads = np.ascontiguousarray(reads, dtype=np.float64)
         d_reads = torch.from_numpy(reads.reshape(-1)).to(dev)
         d_counts = None if read_counts is None else torch.from_numpy(
@@ -459,8 +483,6 @@ class ExactDeviceBatch:
         haps = np.array(haps)
         H = haps.shape[1]
         self.shape = (U, R, M, A, H, int(ploidy))
-        from math import comb
-
         self.G = comb(H + int(ploidy) - 1, int(ploidy))
         self.d_reads = d_reads
         self.d_haps = torch.from_numpy(haps.reshape(-1)).to(dev)
@@ -490,9 +512,6 @@ class ExactDeviceBatch:
         self.d_ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=dev)
         self.out = {}
 
-    def _p(self, t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-
     def _buf(self, name, n, dtype):
         t = self.out.get(name)
         if t is None:
@@ -505,28 +524,17 @@ class ExactDeviceBatch:
         array outputs (likelihoods, posteriors and their summaries)."""
         torch = self.torch
         U, R, M, A, H, K = self.shape
-        o = _lib.ExactOut()
+        f64, outputs = torch.float64, {}
         if streaming:
-            o.mode_alleles = self._buf("mode_alleles", U * K, torch.int64).data_ptr()
-            for nm in ("mode_llk", "mode_prob", "support_prob"):
-                setattr(o, nm, self._buf(nm, U, torch.float64).data_ptr())
-            for nm in ("freqs", "occur"):
-                setattr(o, nm, self._buf(nm, U * H, torch.float64).data_ptr())
+            outputs.update(mode_alleles=(U * K, torch.int64), mode_llk=(U, f64), mode_prob=(U, f64), support_prob=(U, f64),
+                           freqs=(U * H, f64), occur=(U * H, f64))
         if arrays:
-            o.llks = self._buf("llks", U * self.G, torch.float32).data_ptr()
+            outputs.update(llks=(U * self.G, torch.float32), posteriors=(U * self.G, f64), arr_mode_alleles=(U * K, torch.int64),
+                           arr_mode_prob=(U, f64), arr_support_prob=(U, f64), arr_freqs=(U * H, f64), arr_counts=(U * H, f64),
+                           arr_occur=(U * H, f64))
             if llks64:
-                o.llks64 = self._buf("llks64", U * self.G, torch.float64).data_ptr()
-            o.posteriors = self._buf("posteriors", U * self.G, torch.float64).data_ptr()
-            o.arr_mode_alleles = self._buf("arr_mode_alleles", U * K, torch.int64).data_ptr()
-            for nm in ("arr_mode_prob", "arr_support_prob"):
-                setattr(o, nm, self._buf(nm, U, torch.float64).data_ptr())
-            for nm in ("arr_freqs", "arr_counts", "arr_occur"):
-                setattr(o, nm, self._buf(nm, U * H, torch.float64).data_ptr())
-        stream = torch.cuda.current_stream().cuda_stream
-        rc = _lib.lib().mchap_exact_call_batch_device(
-            U, self._p(self.d_reads), R, M, A, self._p(self.d_counts), self._p(self.d_haps), H, K, self.has_prior,
-            self._p(self.d_F), self._p(self.d_fr), C.byref(o), self._p(self.d_ws), C.c_int64(self.ws_bytes), C.c_void_p(stream))
-        _lib.check(rc)
+                outputs["llks64"] = (U * self.G, f64)
+        self._run_only(**outputs)
 
     def _run_only(self, **outputs):
         """mchap_exact_call_batch_device for the named outputs alone ({name: (elements, dtype)}), on torch's current stream."""
@@ -536,8 +544,8 @@ class ExactDeviceBatch:
             setattr(o, nm, self._buf(nm, n, dtype).data_ptr())
         stream = self.torch.cuda.current_stream().cuda_stream
         _lib.check(_lib.lib().mchap_exact_call_batch_device(
-            U, self._p(self.d_reads), R, M, A, self._p(self.d_counts), self._p(self.d_haps), H, K, self.has_prior,
-            self._p(self.d_F), self._p(self.d_fr), C.byref(o), self._p(self.d_ws), C.c_int64(self.ws_bytes), C.c_void_p(stream)))
+            U, _ptr(self.d_reads), R, M, A, _ptr(self.d_counts), _ptr(self.d_haps), H, K, self.has_prior,
+            _ptr(self.d_F), _ptr(self.d_fr), C.byref(o), _ptr(self.d_ws), C.c_int64(self.ws_bytes), C.c_void_p(stream)))
 
     def run_llks64(self):
         """The unrounded float64 likelihoods [U * G] alone, left on the device (what the frequency estimate keeps resident)."""
@@ -586,7 +594,7 @@ class ExactFrequencyEstimate:
     def __init__(self, record_haps, frequencies, n_samples, ploidy_total, device=None):
         torch = _torch()
         self.torch = torch
-        self.device = dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.device = dev = _device(torch, device)
         fr = np.ascontiguousarray(frequencies, dtype=np.float64)
         self.n_records, self.stride = fr.shape
         self.n_samples, self.ploidy_total = int(n_samples), float(ploidy_total)
@@ -605,8 +613,6 @@ class ExactFrequencyEstimate:
         """The units of one shape (n_haps, ploidy): llks64 a float64 torch tensor [U * G] on the device (kept, not copied);
         inbreeding [U]; unit_record / unit_sample [U]: the record of the sub-block and the sample index of each unit."""
         torch, dev = self.torch, self.device
-        from math import comb
-
         rec = np.ascontiguousarray(unit_record, dtype=np.int32)
         smp = np.ascontiguousarray(unit_sample, dtype=np.int32)
         U = len(rec)
@@ -631,15 +637,15 @@ class ExactFrequencyEstimate:
     def step(self, tolerance, max_iterations):
         """One iteration, enqueued on torch's current stream: the counts launches, then the update launch."""
         L = _lib.lib()
-        p = lambda t: C.c_void_p(t.data_ptr())
         stream = C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
         for g in self.groups:
-            _lib.check(L.mchap_exact_em_counts_device(g["U"], p(g["llks"]), g["H"], g["K"], p(g["F"]), p(g["rec"]), p(g["slot"]),
-                                                      p(self.d_freqs), self.stride, p(self.d_active), p(self.d_slab), p(g["ws"]),
-                                                      C.c_int64(g["wsb"]), stream))
-        _lib.check(L.mchap_exact_em_update_device(self.n_records, self.n_samples, p(self.d_haps), self.stride, p(self.d_slab),
-                                                  C.c_double(self.ploidy_total), C.c_double(float(tolerance)), int(max_iterations),
-                                                  p(self.d_freqs), p(self.d_iters), p(self.d_active), p(self.d_delta), stream))
+            _lib.check(L.mchap_exact_em_counts_device(
+                g["U"], _ptr(g["llks"]), g["H"], g["K"], _ptr(g["F"]), _ptr(g["rec"]), _ptr(g["slot"]), _ptr(self.d_freqs), self.stride,
+                _ptr(self.d_active), _ptr(self.d_slab), _ptr(g["ws"]), C.c_int64(g["wsb"]), stream))
+        _lib.check(L.mchap_exact_em_update_device(
+            self.n_records, self.n_samples, _ptr(self.d_haps), self.stride, _ptr(self.d_slab), C.c_double(self.ploidy_total),
+            C.c_double(float(tolerance)), int(max_iterations), _ptr(self.d_freqs), _ptr(self.d_iters), _ptr(self.d_active),
+            _ptr(self.d_delta), stream))
         self.launches += 1
 
     def n_active(self):
@@ -676,8 +682,7 @@ class DenovoRaggedBatch(_OwnBuffers):
     def __init__(self, model: DenovoMCMC, units, device=None):
         torch = _torch()
         self.torch = torch
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        dev = self.device
+        self.device = dev = _device(torch, device)
         self.model = model
         U = len(units)
         Cn, S = int(model.chains), int(model.steps)
@@ -718,48 +723,10 @@ class DenovoRaggedBatch(_OwnBuffers):
             F = u.get("inbreeding")
             D["inbreeding"] = np.nan if F is None else float(F)
             D["stream_id"] = int(u.get("stream_id", 0))
-        self.units_host = desc
-        self.n_units = U
-        self.cfg = model._cfg(self.max_pos)
-        # uint64 words per haplotype of the traces: 2 when the batch holds a unit of more than 62 SNVs / 64 bits per haplotype
-        self.wph = int(_lib.lib().mchap_denovo_trace_words_per_haplotype(C.byref(self.cfg), U, _lib.ptr(desc)))
-        if self.wph < 1:
-            raise NotImplementedError("mchap_hip: unsupported unit shape (" + _lib.last_error() + ")")
-        desc["trace_off"] *= self.wph
-        t_off *= self.wph
-        self.d_units = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(dev)
+        self._allocate(desc, t_off, l_off, f_off)   # (refuses before anything large is uploaded)
         self.d_reads = torch.from_numpy(np.concatenate(r_parts)).to(dev)
         self.d_counts = torch.from_numpy(np.concatenate(c_parts)).to(dev) if c_parts else None
         self.d_nalleles = torch.from_numpy(np.concatenate(a_parts)).to(dev)
-        self.d_trace = torch.empty(t_off, dtype=torch.int64, device=dev)
-        self.d_llks = torch.empty(l_off, dtype=torch.float64, device=dev)
-        self.d_fixed = torch.empty(f_off, dtype=torch.int8, device=dev)
-        self.d_status = torch.empty(U, dtype=torch.int32, device=dev)
-        self.cfg = model._cfg(self.max_pos)
-        self.ws_bytes = int(_lib.lib().mchap_denovo_workspace_bytes(C.byref(self.cfg), U, _lib.ptr(desc)))
-        if self.ws_bytes < 0:
-            raise NotImplementedError("mchap_hip: unsupported unit shape")
-        self.d_ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=dev)
-
-    def _p(self, t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-
-    def _fit(self, stream):
-        """The sampler launch on `stream` (a raw hipStream_t): from the float64 read tensors, or -- a batch built by from_calls --
-        from int8 calls, the tensors formed on the device by the prepare pass (mchap_denovo_fit_batch_calls_device)."""
-        L = _lib.lib()
-        self.cfg.cache_epoch = _lib.next_cache_epoch()
-        if self.d_reads is None:
-            _lib.check(L.mchap_denovo_fit_batch_calls_device(
-                C.byref(self.cfg), self.n_units, self._p(self.d_units), _lib.ptr(self.units_host), self._p(self.d_calls),
-                self._p(self.d_quals), self._p(self.d_qual_prob), int(self.qual_prob_len), self._p(self.d_counts), self._p(self.d_nalleles), None, self._p(self.d_trace),
-                self._p(self.d_llks), self._p(self.d_fixed), self._p(self.d_status), self._p(self.d_ws), C.c_int64(self.ws_bytes),
-                C.c_void_p(stream)))
-            return
-        _lib.check(L.mchap_denovo_fit_batch_device(
-            C.byref(self.cfg), self.n_units, self._p(self.d_units), _lib.ptr(self.units_host), self._p(self.d_reads), self._p(self.d_counts),
-            self._p(self.d_nalleles), None, self._p(self.d_trace), self._p(self.d_llks), self._p(self.d_fixed),
-            self._p(self.d_status), self._p(self.d_ws), C.c_int64(self.ws_bytes), C.c_void_p(stream)))
 
     @classmethod
     def from_calls(cls, model, calls, reads_off, n_reads, n_pos, max_allele, ploidy, counts, counts_off, n_alleles, nalleles_off,
@@ -774,8 +741,7 @@ class DenovoRaggedBatch(_OwnBuffers):
         self = cls.__new__(cls)
         torch = _torch()
         self.torch = torch
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        dev = self.device
+        self.device = dev = _device(torch, device)
         self.model = model
         n_reads, n_pos, ploidy = (np.asarray(x, dtype=np.int64) for x in (n_reads, n_pos, ploidy))
         U = len(n_reads)
@@ -793,37 +759,10 @@ class DenovoRaggedBatch(_OwnBuffers):
         desc["inbreeding"] = np.nan if inbreeding is None else inbreeding
         desc["stream_id"] = 0
         self.Kmax, self.max_pos = int(ploidy.max()), int(n_pos.max())
-        self.units_host, self.n_units = desc, U
-        self.cfg = model._cfg(self.max_pos)
-        self.wph = int(_lib.lib().mchap_denovo_trace_words_per_haplotype(C.byref(self.cfg), U, _lib.ptr(desc)))
-        if self.wph < 1:
-            raise NotImplementedError("mchap_hip: unsupported unit shape (" + _lib.last_error() + ")")
-        desc["trace_off"] *= self.wph
-        self.d_units = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(dev)
-        self.d_reads = None
-        self.d_calls = torch.from_numpy(np.ascontiguousarray(calls, dtype=np.int8)).to(dev)
-        self.d_quals, table = None, np.array([1.0 - error_rate], dtype=np.float64)
-        if quals is not None:
-            from .blockpath import qual_prob_table
-
-            quals = np.ascontiguousarray(quals, dtype=np.int16)
-            assert quals.shape == np.shape(calls)
-            if (quals[np.asarray(calls) >= 0] < 0).any():
-                raise AssertionError("DenovoRaggedBatch.from_calls: a called cell has a negative quality")
-            self.d_quals = torch.from_numpy(quals).to(dev)
-            table = qual_prob_table(error_rate, int(quals.max(initial=0)) + 1)
-        self.qual_prob_len = len(table)
-        self.d_qual_prob = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float64)).to(dev)
+        self._allocate(desc, t.sum(), U * Cn * S, n_pos.sum())
+        self._upload_compact(calls, quals, error_rate, reject_negative="DenovoRaggedBatch.from_calls")
         self.d_counts = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int64)).to(dev) if len(counts) else None
         self.d_nalleles = torch.from_numpy(np.ascontiguousarray(n_alleles, dtype=np.int8)).to(dev)
-        self.d_trace = torch.empty(int(t.sum()) * self.wph, dtype=torch.int64, device=dev)
-        self.d_llks = torch.empty(U * Cn * S, dtype=torch.float64, device=dev)
-        self.d_fixed = torch.empty(int(n_pos.sum()), dtype=torch.int8, device=dev)
-        self.d_status = torch.empty(U, dtype=torch.int32, device=dev)
-        self.ws_bytes = int(_lib.lib().mchap_denovo_workspace_bytes(C.byref(self.cfg), U, _lib.ptr(desc)))
-        if self.ws_bytes < 0:
-            raise NotImplementedError("mchap_hip: unsupported unit shape")
-        self.d_ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=dev)
         return self
 
     def _host_summary(self, u, st, fixed, cache):
@@ -878,12 +817,12 @@ class DenovoRaggedBatch(_OwnBuffers):
         self.p_mode_count = torch.empty(U, dtype=torch.int32, device=dev)
         self.p_mci = torch.empty(U, dtype=torch.int32, device=dev)
         _lib.check(L.mchap_trace_posterior_batch_wph_device(
-            U, self._p(self.d_units), self.S, self.Cn, int(burn), self._p(self.d_trace), int(max_states), K, W, self._p(self.p_words),
-            self._p(self.p_counts), self._p(self.p_n), self._p(self.p_stats), self._p(self.p_mode), self._p(self.p_mode_words),
-            self._p(self.p_mode_count), C.c_void_p(stream)))
+            U, _ptr(self.d_units), self.S, self.Cn, int(burn), _ptr(self.d_trace), int(max_states), K, W, _ptr(self.p_words),
+            _ptr(self.p_counts), _ptr(self.p_n), _ptr(self.p_stats), _ptr(self.p_mode), _ptr(self.p_mode_words),
+            _ptr(self.p_mode_count), C.c_void_p(stream)))
         _lib.check(L.mchap_trace_incongruence_batch_wph_device(
-            U, self._p(self.d_units), self.S, self.Cn, int(burn), self._p(self.d_trace), K, W, C.c_double(float(incongruence_threshold)),
-            self._p(self.p_mci), C.c_void_p(stream)))
+            U, _ptr(self.d_units), self.S, self.Cn, int(burn), _ptr(self.d_trace), K, W, C.c_double(float(incongruence_threshold)),
+            _ptr(self.p_mci), C.c_void_p(stream)))
         self.burn = int(burn)
         self.incongruence_threshold = float(incongruence_threshold)
         self._end()
@@ -902,13 +841,35 @@ class DenovoRaggedBatch(_OwnBuffers):
         o_words = torch.empty(len(over) * cap * K * W, dtype=torch.int64, device=self.device)
         o_counts = torch.empty(len(over) * cap, dtype=torch.int32, device=self.device)
         _lib.check(L.mchap_trace_posterior_listed_wph_device(
-            len(over), self._p(d_list), self._p(self.d_units), self.S, self.Cn, self.burn, self._p(self.d_trace), cap, K, W,
-            self._p(o_words), self._p(o_counts), self._p(self.p_n), self._p(self.p_stats), self._p(self.p_mode),
-            self._p(self.p_mode_words), self._p(self.p_mode_count), C.c_void_p(stream)))
+            len(over), _ptr(d_list), _ptr(self.d_units), self.S, self.Cn, self.burn, _ptr(self.d_trace), cap, K, W,
+            _ptr(o_words), _ptr(o_counts), _ptr(self.p_n), _ptr(self.p_stats), _ptr(self.p_mode),
+            _ptr(self.p_mode_words), _ptr(self.p_mode_count), C.c_void_p(stream)))
         _lib.check(L.mchap_trace_incongruence_listed_wph_device(
-            len(over), self._p(d_list), self._p(self.d_units), self.S, self.Cn, self.burn, self._p(self.d_trace),
-            min(self.S - self.burn, cap), K, W, C.c_double(self.incongruence_threshold), self._p(self.p_mci), C.c_void_p(stream)))
+            len(over), _ptr(d_list), _ptr(self.d_units), self.S, self.Cn, self.burn, _ptr(self.d_trace),
+            min(self.S - self.burn, cap), K, W, C.c_double(self.incongruence_threshold), _ptr(self.p_mci), C.c_void_p(stream)))
         return o_words, o_counts, cap
+
+    def _summary_state(self, only=None):
+        """The summaries of run() on the host, but for the tables of distinct genotypes (they stay on the device: p_words / p_counts,
+        and the listed launch's): (dict(n, stats [U, 2], mode_words [U, K] + two-word axis, mci, status, fixed, total), over, (o_words,
+        o_counts, cap)).  over: the units -- of `only`, by default of all -- whose chains visited more distinct genotypes than the
+        batch kernels keep (samples with few or no reads: their chains wander); they are summarised again on the device with a
+        table that cannot overflow, a list launch over those units only (_summarise_listed: its result, or (None, None, max_states)
+        without such units), and the dict holds what it rewrote -- no trace is downloaded, no posterior formed on the host."""
+        U, K, ms, W = self.n_units, self.Kmax, self.max_states, self.wph
+        self._begin()  # (the pass may have been issued on another stream)
+        status, n, mci = self.d_status.cpu().numpy(), self.p_n.cpu().numpy(), self.p_mci.cpu().numpy()
+        over = np.flatnonzero((status >= 0) & ((n < 0) | (n > ms) | (mci < 0))).astype(np.int32)
+        if only is not None:
+            over = np.intersect1d(over, np.asarray(only, dtype=np.int32)).astype(np.int32)
+        listed = (None, None, ms)
+        if len(over):
+            listed = self._summarise_listed(over)
+            n, mci = self.p_n.cpu().numpy(), self.p_mci.cpu().numpy()
+        state = dict(n=n, stats=self.p_stats.cpu().numpy().reshape(U, 2),
+                     mode_words=self.p_mode_words.cpu().numpy().view(np.uint64).reshape((U, K) + ((W,) if W > 1 else ())),
+                     mci=mci, status=status, fixed=self.d_fixed.cpu().numpy(), total=self.Cn * (self.S - self.burn))
+        return state, over, listed
 
     def summary_arrays(self):
         """The posterior summaries of all units as arrays (what results() turns into one dict per unit): dict(n [U] distinct
@@ -921,19 +882,10 @@ class DenovoRaggedBatch(_OwnBuffers):
         torch = self.torch
         U, K, ms, Wp = self.n_units, self.Kmax, self.max_states, self.wph
         KW = K * Wp   # words of a state (a batch of the general sampler: two words per haplotype, the more significant first)
-        self._begin()
-        status, n, mci = self.d_status.cpu().numpy(), self.p_n.cpu().numpy(), self.p_mci.cpu().numpy()
-        # units with more distinct genotypes than the batch kernels keep (samples with few or no reads: their chains wander):
-        # summarised again by the listed launch, their rows taken from its table
-        over = np.flatnonzero((status >= 0) & ((n < 0) | (n > ms) | (mci < 0))).astype(np.int32)
-        cap = ms
-        if len(over):
-            o_words, o_counts, cap = self._summarise_listed(over)
-            n, mci = self.p_n.cpu().numpy(), self.p_mci.cpu().numpy()
         wshape = (Wp,) if Wp > 1 else ()
-        out = dict(n=n, stats=self.p_stats.cpu().numpy().reshape(U, 2),
-                   mode_words=self.p_mode_words.cpu().numpy().view(np.uint64).reshape((U, K) + wshape),
-                   mci=mci, status=status, fixed=self.d_fixed.cpu().numpy(), total=self.Cn * (self.S - self.burn))
+        # (the units the listed launch summarised again: their rows are taken from its table)
+        out, over, (o_words, o_counts, cap) = self._summary_state()
+        n, mci, status = out["n"], out["mci"], out["status"]
         is_over = np.zeros(U, dtype=bool)
         is_over[over] = True
         out["plain"] = (status >= 0) & (n >= 0) & (n <= np.where(is_over, cap, ms)) & (mci >= 0)
@@ -966,29 +918,12 @@ class DenovoRaggedBatch(_OwnBuffers):
         back as dict(status, limit=reason)."""
         U, K, ms, W = self.n_units, self.Kmax, self.max_states, self.wph
         wshape = (W,) if W > 1 else ()   # (a haplotype of a wide batch is two words: unpack_trace(..., W))
-        self._begin()  # (the pass may have been issued on another stream)
+        state, over, (o_words, o_counts, cap) = self._summary_state(only)
+        n, stats, mode_words, mci, status, fixed, total = (state[k] for k in ("n", "stats", "mode_words", "mci", "status", "fixed", "total"))
         words = self.p_words.cpu().numpy().view(np.uint64).reshape((U, ms, K) + wshape)
         counts = self.p_counts.cpu().numpy().reshape(U, ms)
-        n = self.p_n.cpu().numpy()
-        stats = self.p_stats.cpu().numpy().reshape(U, 2)
-        mode_words = self.p_mode_words.cpu().numpy().view(np.uint64).reshape((U, K) + wshape)
-        mci = self.p_mci.cpu().numpy()
-        status = self.d_status.cpu().numpy()
-        fixed = self.d_fixed.cpu().numpy()
-        total = self.Cn * (self.S - self.burn)
-        # Units whose chains visited more distinct genotypes than the batch kernels keep (samples with few or no reads:
-        # their chains wander): summarised again on the device with a table that cannot overflow, a list launch over
-        # those units only -- no trace is downloaded, no posterior formed on the host
-        over = np.flatnonzero((status >= 0) & ((n < 0) | (n > ms) | (mci < 0))).astype(np.int32)
-        if only is not None:
-            over = np.intersect1d(over, np.asarray(only, dtype=np.int32)).astype(np.int32)
         over_row = {}
         if len(over):
-            o_words, o_counts, cap = self._summarise_listed(over)
-            n = self.p_n.cpu().numpy()
-            stats = self.p_stats.cpu().numpy().reshape(U, 2)
-            mode_words = self.p_mode_words.cpu().numpy().view(np.uint64).reshape((U, K) + wshape)
-            mci = self.p_mci.cpu().numpy()
             ow = o_words.cpu().numpy().view(np.uint64).reshape((len(over), cap, K) + wshape)
             oc = o_counts.cpu().numpy().reshape(len(over), cap)
             over_row = {int(u): (ow[i], oc[i], cap) for i, u in enumerate(over)}

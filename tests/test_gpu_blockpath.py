@@ -63,6 +63,68 @@ def test_from_calls_equals_the_tensor_batch():
         assert np.array_equal(arr["counts"][first[u]: first[u] + arr["n"][u]] / arr["total"], x["probabilities"])
 
 
+def _summary_units():
+    """Six small units of ploidy 2-4: four with 4-10 reads, two with one all-gap read (no information: their chains wander)."""
+    from mchap_amd import encoding
+
+    rng = np.random.default_rng(23)
+    units = []
+    for i, (K, M, R) in enumerate([(2, 3, 4), (4, 5, 0), (3, 4, 10), (4, 4, 0), (2, 5, 7), (4, 3, 6)]):
+        n_alleles = np.full(M, 2)
+        haps = rng.integers(0, 2, size=(K, M))
+        calls = haps[rng.integers(0, K, size=R)].astype(np.int8) if R else np.full((1, M), -1, dtype=np.int8)
+        units.append(dict(reads=encoding.encode_read_distributions(n_alleles, calls, None, error_rate=0.0024), counts=None,
+                          n_alleles=n_alleles, ploidy=K, inbreeding=None, stream_id=i))
+    return units
+
+
+def test_summary_arrays_and_results_describe_the_same_posterior():
+    """summary_arrays() and results() start from one download of the summaries: they must describe the same posterior for every
+    unit, whether its distinct genotypes fit the batch kernels' table (here max_states=4) or come from the listed launch.  (The
+    oracle on the same Philox streams: the two all-gap units visit 79 and 75 distinct genotypes in the 2 x 40 steps after the
+    burn-in, unit 5 visits 15, units 0, 2 and 4 stay on one.)"""
+    import torch
+
+    from mchap_amd import DenovoMCMC
+    from mchap_amd.assemble import unpack_trace
+    from mchap_amd.device import DenovoRaggedBatch
+
+    units = _summary_units()
+    U, ms = len(units), 4
+    model = DenovoMCMC(ploidy=4, n_alleles=[2], steps=60, chains=2, random_seed=7)
+    b = DenovoRaggedBatch(model, units)
+    b.run(20, max_states=ms)
+    torch.cuda.synchronize()
+    arr = b.summary_arrays()
+    res = b.results(raise_on_limit=False)
+    listed = np.flatnonzero(arr["n"] > ms)
+    assert {1, 3} <= set(listed.tolist()) and (arr["n"] <= ms).any()   # both kinds of unit are in the batch
+    assert arr["plain"].all() and arr["total"] == 2 * 40 and len(res) == U
+    assert len(arr["words"]) == len(arr["counts"]) == int(arr["n"].sum())
+    first = np.cumsum(arr["n"]) - arr["n"]
+
+    def same(u, x):
+        D = b.units_host[u]
+        K, M, A = int(D["ploidy"]), int(D["n_pos"]), int(D["max_allele"])
+        fx = arr["fixed"][int(D["fixed_off"]): int(D["fixed_off"]) + M]
+        rows = slice(first[u], first[u] + arr["n"][u])
+        assert np.array_equal(unpack_trace(arr["words"][rows, :K], fx, A), x["genotypes"])
+        assert np.array_equal(arr["counts"][rows] / arr["total"], x["probabilities"])
+        assert arr["counts"][rows].sum() == arr["total"]
+        assert (arr["stats"][u, 0], arr["stats"][u, 1]) == (x["spm"], x["gpm"])
+        assert np.array_equal(unpack_trace(arr["mode_words"][u, :K], fx, A), x["mode_genotype"])
+        assert arr["mci"][u] == x["mci"] and arr["status"][u] == x["status"]
+
+    for u, x in enumerate(res):
+        same(u, x)
+    only = [3, 0, 4]   # (one of the listed launch, two plain)
+    for u, x in zip(only, b.results(raise_on_limit=False, only=only)):
+        same(u, x)
+        for k in ("genotypes", "probabilities", "mode_genotype"):
+            assert np.array_equal(x[k], res[u][k])
+        assert (x["spm"], x["gpm"], x["mci"], x["status"]) == (res[u]["spm"], res[u]["gpm"], res[u]["mci"], res[u]["status"])
+
+
 def _both(tmp_path=None, **kw):
     from mchap_amd import application
 
