@@ -218,7 +218,11 @@ int mchap_wave_sum_batch(const double *x, int64_t n_waves, double *out);
  *                                                         of the mode support
  *   mode_words  uint64 [n_units][ploidy_max] or NULL      that genotype itself, whatever its rank
  *   mode_count  int32  [n_units] or NULL                  its occurrences
- * post_n < 0: more than 512 distinct genotypes (-n: counts beyond the 512th are lost; fall back to the trace);
+ * post_n < 0: more than 512 distinct genotypes -- the table overflowed: read the sign only.  A genotype beyond the table is not
+ * indexed and counts again in every batch of 64 states it reappears in, so -post_n is an upper bound of the number of distinct
+ * genotypes (at least that number, at most the states of the trace), not the number.  The per-state outputs then rank the first
+ * 512 distinct genotypes alone, each with all its occurrences, and the mode_* outputs are not the summary's (fall back to the listed
+ * form below, or to the trace).  A table that is exactly full (512 distinct genotypes) does not overflow: post_n = 512.
  * INT32_MIN: the unit's ploidy exceeds ploidy_max. */
 int mchap_trace_posterior_batch_device(int n_units, const mchap_unit *units_dev, int steps, int chains, int burn,
                                        const uint64_t *trace_words, int max_states, int ploidy_max,

@@ -94,6 +94,52 @@ def _null_buffer_calls(L):
     ]
 
 
+def test_trace_summaries_refuse_on_the_host():
+    """What launch_posterior / launch_incongruence (csrc/posterior_api.hip) turn away before the device is touched: every buffer is
+    a non-NULL address that is never read."""
+    import ctypes as C
+
+    from mchap_amd import _lib
+
+    L = _lib.lib()
+    L.mchap_trace_posterior_max_states_wph.restype = C.c_int
+    scratch = C.create_string_buffer(64)
+    b = C.c_void_p(C.addressof(scratch))
+    thr = C.c_double(0.6)
+
+    def posterior(steps=10, chains=2, burn=0, ploidy_max=4, wph=1, cap=None):
+        if cap is None:
+            return L.mchap_trace_posterior_batch_wph_device(1, b, steps, chains, burn, b, 4, ploidy_max, wph, b, b, b, b, b, b, b, None)
+        return L.mchap_trace_posterior_listed_wph_device(1, b, b, steps, chains, burn, b, cap, ploidy_max, wph, b, b, b, b, b, b, b, None)
+
+    def incongruence(steps=10, chains=2, burn=0, ploidy_max=4, wph=1, cap=None):
+        if cap is None:
+            return L.mchap_trace_incongruence_batch_wph_device(1, b, steps, chains, burn, b, ploidy_max, wph, thr, b, None)
+        return L.mchap_trace_incongruence_listed_wph_device(1, b, b, steps, chains, burn, b, cap, ploidy_max, wph, thr, b, None)
+
+    for call in (posterior, incongruence):
+        for burn in (10, 11, -1):
+            assert call(burn=burn) == _lib.ERR_BAD_ARG and L.mchap_last_error() == b"burn must be in [0, steps)", (call.__name__, burn)
+        assert call(wph=3) == _lib.ERR_LIMIT and L.mchap_last_error() == b"ploidy_max 4 at 3 word(s) per haplotype out of range"
+        assert call(ploidy_max=9) == _lib.ERR_LIMIT and L.mchap_last_error() == b"ploidy_max 9 at 1 word(s) per haplotype out of range"
+        assert call(ploidy_max=16, wph=2) == _lib.ERR_LIMIT
+        for pm, wph in ((4, 1), (8, 1), (15, 2)):
+            most = int(L.mchap_trace_posterior_max_states_wph(pm, wph))
+            assert most >= 512
+            assert call(ploidy_max=pm, wph=wph, cap=most + 1) == _lib.ERR_LIMIT
+            assert (b"a table of %d states does not fit the LDS at ploidy %d (at most %d)" % (most + 1, pm, most)) == L.mchap_last_error()
+    assert incongruence(cap=0) == _lib.ERR_LIMIT
+    assert posterior(cap=0) == _lib.ERR_BAD_ARG and L.mchap_last_error() == b"max_states must be >= 1"   # (a listed call's rows are its table)
+    assert L.mchap_trace_posterior_max_states_wph(9, 1) == 0 and L.mchap_trace_posterior_max_states_wph(4, 3) == 0
+    assert incongruence(chains=33) == _lib.ERR_LIMIT and L.mchap_last_error() == b"chains must be in 1..32"
+    assert incongruence(chains=0) == _lib.ERR_LIMIT
+    # the calling form goes through the same checks
+    assert L.mchap_call_incongruence_batch_device(1, b, 10, 33, 0, b, 4, thr, b, None) == _lib.ERR_LIMIT
+    assert L.mchap_last_error() == b"chains must be in 1..32"
+    assert L.mchap_call_incongruence_listed_device(1, b, b, 10, 2, 10, b, 70, 4, thr, b, None) == _lib.ERR_BAD_ARG
+    assert L.mchap_call_incongruence_batch_device(1, b, 10, 2, 0, b, 9, thr, b, None) == _lib.ERR_LIMIT
+
+
 @pytest.fixture(params=["", "1"], ids=["libmchap_hip", "libmchap_hip_test"])
 def either_library(request, monkeypatch):
     from mchap_amd import _lib
