@@ -12,6 +12,7 @@
 // Philox streams as in philox.hpp: key (seed, unit stream), counter word 2 = chain << 16, draws in the reference's order: K - 1 shuffle draws, then one uniform per sub-step.
 #pragma once
 #include "exact_kernel.hpp"
+#include "philox.hpp"
 
 namespace mchap {
 

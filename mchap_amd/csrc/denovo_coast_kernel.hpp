@@ -26,7 +26,7 @@
 // handed-back chains, which are few (23 of 20 000 at configs[1]): NW x 64 steps per sweep, 0.25 -> 0.08 ms per launch --;
 // dynamic LDS coast_lds_bytes(Mmax).
 #pragma once
-#include "denovo_spec_kernel.hpp"
+#include "denovo_common.hpp"
 
 namespace mchap {
 

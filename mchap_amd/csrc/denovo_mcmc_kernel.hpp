@@ -1,7 +1,7 @@
 // De-novo MCMC haplotype assembler for MI355X (gfx950): one (locus x sample) unit per
 // workgroup, one wavefront per chain, lanes over reads.
 //
-// Reference path (all paths relative to /root/reference/mchap/):
+// Reference path (all paths relative to the reference's mchap/ package):
 //   DenovoMCMC.fit/_mcmc            assemble/mcmc.py:103-265
 //   _denovo_assembler               assemble/mcmc.py:268-426
 //   mutation.base_step/compound     assemble/mutation.py:14-246
@@ -20,274 +20,13 @@
 // one packed uint64 (position 0 in the most significant field), so haplotype equality,
 // segment labels and the canonical sort are integer compares.  All chain state is
 // wave-private; after the staging barrier the chains of a unit never synchronise.
+//
+// Kernel 1: only the parity suite's library ships it (v1_inst.hip).  The chain context, its LDS layout and the likelihood
+// evaluation are in denovo_llk_kernel.hpp, which the shipped library's likelihood test hook shares.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/mchap_hip.h"
-#include "philox.hpp"
+#include "denovo_llk_kernel.hpp"
 
 namespace mchap {
-
-constexpr int WAVE = 64;
-constexpr uint32_t SLOT_INIT = 0xFFFFu;
-
-// log(n), log(1/n) for small n, computed by the host's libm at library load.
-static __constant__ double c_ln[260];      // per translation unit (the library is built from several)
-static __constant__ double c_ln_inv[260];
-
-struct DenovoParams {
-  const mchap_unit *units;
-  const double *reads;
-  const int64_t *counts;
-  const int8_t *n_alleles;
-  const int8_t *initial;
-  uint64_t *trace;
-  double *llks;
-  int8_t *fixed;
-  int32_t *status;
-  const double *break_table;  // device copy, [(max_pos+1)][max_pos]
-  int max_pos;
-  int steps, chains, n_temps, n_intervals;
-  double temps[MCHAP_MAX_TEMPS];
-  double fix_hom, p_recomb, p_partial, p_dosage;
-  uint64_t seed;
-  int rpad;  // 64 * RPL
-  // optional per-chain likelihood cache in HBM/L2: [units*chains][cache_slots] of {tag, llk}; 0 slots = off
-  uint64_t *cache;
-  int cache_slots;  // power of two
-  // genotypes wider than 63 bits are tagged by a hash; their full words [units*chains][cache_slots][cache_key_words]
-  // are kept beside the entries and compared on every tag match, so a hit is always the genotype itself
-  // (cache_key_words = the batch's largest ploidy; 0 when every unit's genotypes fit the tag)
-  uint64_t *cache_keys;
-  int cache_key_words;
-  // compact input (kernels 2 / 3 only): int8 allele calls [R][M0] per unit instead of the float64 tensor, optional
-  // int16 base qualities, and the probability of a correct call per quality (qual_prob[0] when there are none)
-  const int8_t *calls;
-  const int16_t *quals;
-  const double *qual_prob;
-  int qual_prob_len;
-};
-
-// ---- wave-private LDS scratch -------------------------------------------------------------
-struct WaveLayout {
-  int w, pw, llk, rngn, sub, shift, hetrow, nal, probs, llks, optin, prior, buf, total;
-};
-
-__host__ __device__ inline int align8(int x) { return (x + 7) & ~7; }
-
-__host__ __device__ inline int snv_genotypes(int n_alleles, int ploidy) {
-  // C(n + k - 1, k)
-  long r = 1;
-  for (int d = 1; d <= ploidy; d++) r = r * (n_alleles - 1 + d) / d;
-  return (int)r;
-}
-
-__host__ __device__ inline WaveLayout wave_layout(int K, int M, int A, int T) {
-  WaveLayout L;
-  int o = 0;
-  L.w = o; o += 8 * T * K;
-  L.pw = o; o += 8 * K;
-  L.llk = o; o += 8 * T;
-  L.rngn = o; o += 8 * (T + 1);
-  L.probs = o; o += 8 * (K * K + 2 > A ? K * K + 2 : A);
-  L.llks = o; o += 8 * (K * K + 2 > A ? K * K + 2 : A);
-  L.prior = o; o += 8 * (2 * (K + 1) + 4);
-  int nb = snv_genotypes(A, K);
-  if (nb < M * A) nb = M * A;
-  if (nb < M + 4) nb = M + 4;  // also holds the interval end points of a structural step (ints)
-  L.buf = o; o += 8 * nb;
-  L.optin = o; o += 4 * K * K;
-  L.sub = o; o += align8(2 * K * M);
-  L.hetrow = o; o += align8(2 * M);
-  L.shift = o; o += align8(M);
-  L.nal = o; o += align8(M);
-  L.total = align8(o);
-  return L;
-}
-
-__host__ __device__ inline int allele_bits(int A) { return A <= 2 ? 1 : (A <= 4 ? 2 : 3); }
-
-// ---- small device helpers ------------------------------------------------------------------
-// Sum over the 64 lanes, in every lane, associated as the XOR butterfly 32, 16, 8, 4, 2, 1 associates it (every likelihood of
-// every kernel goes through this tree: the bits of a value must not depend on which kernel formed it).  The two steps across rows of
-// 16 lanes are ds_bpermute round trips; inside a row the partners come through DPP row rotations (round 4: ~10 instead of ~100
-// cycles of latency per step).  row_ror:8 reads lane (i + 8) mod 16 = i ^ 8 of the row; after that step the row's values have period
-// 8, so row_ror:4 reads a lane holding exactly the value of lane i ^ 4 -- and so on: the same operands in every addition (a + b
-// is b + a bit for bit), hence the same bits as the plain butterfly (tests/test_gpu_read_log.py::test_wave_sum_tree).
-template <int CTRL>
-__device__ __forceinline__ double wave_dpp_f64(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)((unsigned long long)b >> 32), CTRL, 0xf, 0xf, false);
-  return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#ifdef MCHAP_PLAIN_BUTTERFLY
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, WAVE);
-#else
-  v += __shfl_xor(v, 32, WAVE);
-  v += __shfl_xor(v, 16, WAVE);
-  v += wave_dpp_f64<0x128>(v);  // row_ror:8
-  v += wave_dpp_f64<0x124>(v);  // row_ror:4
-  v += wave_dpp_f64<0x122>(v);  // row_ror:2
-  v += wave_dpp_f64<0x121>(v);  // row_ror:1
-#endif
-  return v;
-}
-// test hook (mchap_wave_sum_batch): one wavefront per 64 values; every lane must hold the same sum
-static __global__ void wave_sum_kernel(const double *x, double *out) {
-  const double s = wave_sum(x[(size_t)blockIdx.x * WAVE + threadIdx.x]);
-  const bool same = __ballot(__double_as_longlong(s) == __double_as_longlong(__shfl(s, 0, WAVE))) == ~0ull;
-  if (threadIdx.x == 0) out[blockIdx.x] = same ? s : __longlong_as_double(0x7ff8dead00000000ll);
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, WAVE);
-  return v;
-}
-
-__device__ __forceinline__ uint32_t nib(uint32_t p, int h) { return (p >> (4 * h)) & 15u; }
-__device__ __forceinline__ uint32_t nib_set(uint32_t p, int h, uint32_t v) {
-  return (p & ~(15u << (4 * h))) | (v << (4 * h));
-}
-// ... and packs of sixteen nibbles (ploidies 9 to 15: the general lanes-over-chains sampler, denovo_simt_kernel<0, u128>)
-__device__ __forceinline__ uint32_t nib(uint64_t p, int h) { return (uint32_t)(p >> (4 * h)) & 15u; }
-__device__ __forceinline__ uint64_t nib_set(uint64_t p, int h, uint32_t v) {
-  return (p & ~(15ull << (4 * h))) | ((uint64_t)v << (4 * h));
-}
-
-// jitutils.py:7-26
-__device__ __forceinline__ double add_log_prob(double x, double y) {
-  if (x == -INFINITY && y == -INFINITY) return -INFINITY;
-  if (x > y) return x + log1p(exp(y - x));
-  return y + log1p(exp(x - y));
-}
-
-// jitutils.py:77-92: searchsorted(cumsum(p), u, side="right")
-__device__ __forceinline__ int choose_from(const double *p, int n, double u) {
-  double c = 0.0;
-  for (int i = 0; i < n; i++) {
-    c += p[i];
-    if (c > u) return i;
-  }
-  return n;
-}
-
-// first-occurrence dosage of the rows (in[h], out[h]) (jitutils.py:378-422 on label rows);
-// a zero nibble marks a duplicate.
-template <class P>
-__device__ __forceinline__ P dosage_of_labels(P in, P out, int K, bool use_out) {
-  P d = 0;
-  for (int h = 0; h < K; h++) d |= (P)1 << (4 * h);
-  for (int h = 0; h < K; h++) {
-    if (nib(d, h) == 0) continue;
-    for (int p = h + 1; p < K; p++) {
-      if (nib(d, p) == 0) continue;
-      if (nib(in, h) == nib(in, p) && (!use_out || nib(out, h) == nib(out, p))) {
-        d += (P)1 << (4 * h);
-        d &= ~((P)15 << (4 * p));
-      }
-    }
-  }
-  return d;
-}
-
-// structural.py:74-118
-template <class P>
-__device__ __forceinline__ int recombination_n_options(P in, P out, int K) {
-  const P d = dosage_of_labels(in, out, K, true);
-  int n = 0;
-  for (int h0 = 0; h0 < K; h0++) {
-    if (nib(d, h0) == 0) continue;
-    for (int h1 = h0 + 1; h1 < K; h1++) {
-      if (nib(d, h1) == 0) continue;
-      if (nib(in, h0) == nib(in, h1) || nib(out, h0) == nib(out, h1)) continue;
-      n++;
-    }
-  }
-  return n;
-}
-
-// structural.py:181-237
-template <class P>
-__device__ __forceinline__ int dosage_n_options(P in, P out, int K) {
-  const P hd = dosage_of_labels(in, out, K, true);
-  const P sd = dosage_of_labels(in, out, K, false);
-  int n = 0;
-  for (int h0 = 0; h0 < K; h0++) {
-    if (nib(hd, h0) == 0) continue;
-    if (nib(sd, h0) == 1) continue;
-    for (int h1 = 0; h1 < K; h1++) {
-      if (nib(sd, h1) == 0) continue;
-      if (nib(in, h0) == nib(in, h1)) continue;
-      n++;
-    }
-  }
-  return n;
-}
-
-// structural.py:121-178 / 240-307: option i = the `in` label pack after the move
-__device__ inline int step_options(uint32_t in, uint32_t out, int K, int step_type, uint32_t *opt) {
-  const uint32_t hd = dosage_of_labels(in, out, K, true);
-  int n = 0;
-  if (step_type == 0) {
-    for (int h0 = 0; h0 < K; h0++) {
-      if (nib(hd, h0) == 0) continue;
-      for (int h1 = h0 + 1; h1 < K; h1++) {
-        if (nib(hd, h1) == 0) continue;
-        if (nib(in, h0) == nib(in, h1) || nib(out, h0) == nib(out, h1)) continue;
-        uint32_t o = nib_set(in, h0, nib(in, h1));
-        o = nib_set(o, h1, nib(in, h0));
-        opt[n++] = o;
-      }
-    }
-  } else {
-    const uint32_t sd = dosage_of_labels(in, out, K, false);
-    for (int h0 = 0; h0 < K; h0++) {
-      if (nib(hd, h0) == 0) continue;
-      if (nib(sd, h0) == 1) continue;
-      for (int h1 = 0; h1 < K; h1++) {
-        if (nib(sd, h1) == 0) continue;
-        if (nib(in, h0) == nib(in, h1)) continue;
-        opt[n++] = nib_set(in, h0, nib(in, h1));
-      }
-    }
-  }
-  return n;
-}
-
-// ---- per-chain context -------------------------------------------------------------------
-struct Chain {
-  // LDS
-  const double *rl;   // staged reads [M0*A][rpad]
-  uint64_t *w;        // [T][K] haplotype words per temperature
-  uint64_t *pw;       // [K] proposal
-  double *llk_t;      // [T]
-  uint64_t *rngn;     // [T+1] draw counters
-  double *probs, *llks;
-  double *prior_tab;  // [0..K] lg(dose+disp) - (lg(dose+1)+lg(disp)); [K+1..2K+1] lg(dose+1); then left, lgK1, K*luh
-  double *buf;
-  uint32_t *optin;
-  uint16_t *sub;
-  uint16_t *hetrow;   // het position * A
-  uint8_t *shift;
-  uint8_t *nal;       // n_alleles of het positions
-  // scalars
-  int K, Mh, A, T, rpad, lane;
-  uint32_t amask;
-  int bits;
-  double invK;
-  double inbreeding;  // NaN == None
-  double luh;
-  Rng rng;
-  uint64_t *cache;   // this chain's {tag, value} table or nullptr
-  uint32_t cache_mask;
-  int key_bits;      // bits per haplotype word actually used (Mh * bits)
-  bool w01;          // every read weight of the unit is 0 or 1: one logarithm per group of four chunks (read_log_sum_chunks)
-};
 
 // Likelihood cache: the reference memoises log_likelihood per genotype in an array-backed trie
 // (assemble/likelihood.py:151-305, arraymap.py) because a converged chain keeps proposing the same
@@ -295,12 +34,6 @@ struct Chain {
 // table per chain in global memory (L2 / Infinity Cache resident), keyed by the exact packed genotype
 // when it fits 63 bits, else by a 64-bit mix of the haplotype words; the stored value is the llk this
 // same kernel computed for that key, so hits return bit-identical values.
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
 __device__ __forceinline__ uint64_t genotype_tag(const Chain &c, const uint64_t *hw) {
   uint64_t t = 0;
   if (c.key_bits * c.K <= 63) {
@@ -309,28 +42,6 @@ __device__ __forceinline__ uint64_t genotype_tag(const Chain &c, const uint64_t 
     for (int h = 0; h < c.K; h++) t = mix64(t ^ hw[h]) + 0x9E3779B97F4A7C15ull;
   }
   return (t << 1) | 1ull;
-}
-
-template <int RPL>
-__device__ __forceinline__ double eval_llk(const Chain &c, const uint64_t *hw, const double (&cnt)[RPL]) {
-  double acc[RPL];
-#pragma unroll
-  for (int i = 0; i < RPL; i++) acc[i] = 0.0;
-  for (int h = 0; h < c.K; h++) {
-    const uint64_t wh = hw[h];
-    double prod[RPL];
-#pragma unroll
-    for (int i = 0; i < RPL; i++) prod[i] = 1.0;
-    for (int j = 0; j < c.Mh; j++) {
-      const uint32_t a = (uint32_t)(wh >> c.shift[j]) & c.amask;
-      const double *row = c.rl + (size_t)(c.hetrow[j] + a) * c.rpad + c.lane;
-#pragma unroll
-      for (int i = 0; i < RPL; i++) prod[i] *= row[WAVE * i];
-    }
-#pragma unroll
-    for (int i = 0; i < RPL; i++) acc[i] += prod[i] * c.invK;
-  }
-  return wave_sum(read_log_sum_chunks<RPL>(acc, cnt, c.w01));
 }
 
 template <int RPL>
@@ -596,52 +307,6 @@ __device__ inline void chain_swap_step(Chain &c, uint64_t *wi, double &llk_i, do
     llk_j = t;
   }
 }
-
-// calling/prior.py:116-179 with frequencies=None, on a nibble-packed SNV genotype (snpcalling.py:55-60)
-__device__ inline double snv_log_prior(uint32_t g, int K, int n_alleles, double F) {
-  // allelic dosage, first-occurrence convention (calling/utils.py:7-35)
-  int dose[MCHAP_MAX_PLOIDY];
-  for (int i = 0; i < K; i++) dose[i] = 0;
-  for (int i = 0; i < K; i++) {
-    int j = 0;
-    while (nib(g, i) != nib(g, j)) j++;
-    dose[j] += 1;
-  }
-  if (F == 0.0) {
-    double den = 0.0;
-    for (int i = 0; i < K; i++) den += lgamma((double)dose[i] + 1.0);
-    return (lgamma((double)K + 1.0) - den) - (double)K * c_ln[n_alleles];
-  }
-  const double alpha = (1.0 / (double)n_alleles) * ((1.0 - F) / F);
-  const double sum_alphas = alpha * (double)n_alleles;
-  const double left = (lgamma((double)K + 1.0) + lgamma(sum_alphas)) - lgamma((double)K + sum_alphas);
-  double prod = 0.0;
-  for (int i = 0; i < K; i++) {
-    if (dose[i] > 0) prod += lgamma((double)dose[i] + alpha) - (lgamma((double)dose[i] + 1.0) + lgamma(alpha));
-  }
-  return left + prod;
-}
-
-// jitutils.py:114-146 on a nibble pack
-template <class P>
-__device__ inline P increment_snv_genotype(P g, int K) {
-  if (K == 1) return g + 1;
-  const uint32_t previous = nib(g, 0);
-  for (int i = 1; i < K; i++) {
-    const uint32_t allele = nib(g, i);
-    if (allele == previous) continue;
-    // allele > previous
-    const int k = i - 1;
-    g = nib_set(g, k, nib(g, k) + 1);
-    for (int z = 0; z < k; z++) g = nib_set(g, z, 0);
-    return g;
-  }
-  g = nib_set(g, K - 1, nib(g, K - 1) + 1);
-  for (int z = 0; z < K - 1; z++) g = nib_set(g, z, 0);
-  return g;
-}
-
-constexpr int CHAINS_PER_BLOCK = 4;
 
 // grid = (units, ceil(chains / CHAINS_PER_BLOCK)); block = 64 * min(chains, CHAINS_PER_BLOCK)
 template <int RPL>
@@ -941,65 +606,6 @@ __global__ __launch_bounds__(64 * CHAINS_PER_BLOCK) void denovo_mcmc_kernel(cons
     if (lane == 0) P.llks[llk_base + step] = c.llk_t[T - 1];
   }
   if (lane == 0 && status != MCHAP_UNIT_OK) atomicMax(&P.status[blockIdx.x], status);
-}
-
-// Test hook: log_likelihood (assemble/likelihood.py:17-70) of many genotypes of one unit; one wavefront
-// per genotype, same staging and evaluation code as the sampler.
-template <int RPL>
-__global__ __launch_bounds__(256) void llk_batch_kernel(const double *reads, int R, int M, int A, const int64_t *counts,
-                                                        const int8_t *genotypes, int n_genotypes, int K, int rpad,
-                                                        double *out) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  double *rl = reinterpret_cast<double *>(smem);
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int MA = M * A;
-  for (int r = threadIdx.x; r < rpad; r += blockDim.x) {
-    for (int q = 0; q < MA; q++) {
-      const double v = r < R ? reads[(size_t)r * MA + q] : 1.0;
-      rl[(size_t)q * rpad + r] = isnan(v) ? 1.0 : v;
-    }
-  }
-  double cnt[RPL];
-#pragma unroll
-  for (int i = 0; i < RPL; i++) {
-    const int r = lane + WAVE * i;
-    cnt[i] = (r < R) ? (counts ? (double)counts[r] : 1.0) : 0.0;
-  }
-  bool w01_l = true;
-#pragma unroll
-  for (int i = 0; i < RPL; i++) w01_l = w01_l && (cnt[i] == 0.0 || cnt[i] == 1.0);
-  unsigned char *ws = smem + (size_t)MA * rpad * sizeof(double) + (size_t)wave * (8 * K + 4 * M + 64);
-  Chain c;
-  c.w01 = __ballot(!w01_l) == 0ull;  // (the samplers' rule: one logarithm per group of four chunks where the weights are 0 / 1)
-  c.rl = rl;
-  c.pw = reinterpret_cast<uint64_t *>(ws);
-  c.hetrow = reinterpret_cast<uint16_t *>(ws + 8 * K);
-  c.shift = ws + 8 * K + align8(2 * M);
-  c.K = K;
-  c.Mh = M;
-  c.A = A;
-  c.rpad = rpad;
-  c.lane = lane;
-  c.invK = 1.0 / (double)K;
-  c.bits = allele_bits(A);
-  c.amask = (1u << c.bits) - 1u;
-  for (int j = 0; j < M; j++) {
-    c.hetrow[j] = (uint16_t)(j * A);
-    c.shift[j] = (uint8_t)(c.bits * (M - 1 - j));
-  }
-  __syncthreads();
-  const int nw = blockDim.x / WAVE;
-  for (int g = blockIdx.x * nw + wave; g < n_genotypes; g += gridDim.x * nw) {
-    const int8_t *gt = genotypes + (size_t)g * K * M;
-    for (int h = 0; h < K; h++) {
-      uint64_t x = 0;
-      for (int j = 0; j < M; j++) x |= (uint64_t)(uint8_t)gt[h * M + j] << c.shift[j];
-      c.pw[h] = x;
-    }
-    const double llk = eval_llk<RPL>(c, c.pw, cnt);
-    if (lane == 0) out[g] = llk;
-  }
 }
 
 }  // namespace mchap

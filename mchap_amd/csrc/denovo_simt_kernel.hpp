@@ -4,467 +4,20 @@
 // genotypes: with the reference's own likelihood cache (assemble/likelihood.py:151-305) 99.6 % of the requested
 // likelihood evaluations are cache hits (69.2 k requests -> 280 evaluations per locus, measured with the CPU
 // port).  What remains is the sequential book-keeping of ~40 dependent sub-steps per MCMC step: integer label /
-// dosage logic, one exp, one uniform draw, one cache probe.  A wavefront per chain (denovo_kernel.hpp) executes
+// dosage logic, one exp, one uniform draw, one cache probe.  A wavefront per chain (denovo_mcmc_kernel.hpp) executes
 // that scalar work on 1 of 64 lanes; here every lane runs its own chain, so the same instruction stream advances
 // 64 chains, and the wavefront only co-operates (lanes over reads, wave shuffle reduction) when a lane misses its
 // cache.
 //
-// Pipeline: denovo_prepare_kernel (one workgroup per unit: homozygous fix, read tensor transposed to
-// [M0*A][RPAD] with NaN -> 1 in the workspace, initial-genotype distribution, prior tables) ->
+// Pipeline: denovo_prepare_kernel (denovo_prepare_kernel.hpp: one workgroup per unit: homozygous fix, read tensor transposed
+// to [M0*A][RPAD] with NaN -> 1 in the workspace, initial-genotype distribution, prior tables) ->
 // denovo_simt_kernel (one wavefront per 64 chains).  Same algorithm, same Philox streams and therefore the same
-// traces as denovo_mcmc_kernel; reference citations as in denovo_kernel.hpp.
+// traces as denovo_mcmc_kernel; reference citations as in denovo_mcmc_kernel.hpp.  The launch parameters, the prepare pass's
+// metadata and the helpers shared with the other samplers are in denovo_common.hpp.
 #pragma once
-#include "denovo_kernel.hpp"
+#include "denovo_common.hpp"
 
 namespace mchap {
-
-// per-unit metadata written by the prepare kernel
-constexpr int META_I_MH = 0;      // number of sampled (non-fixed) positions
-constexpr int META_I_STATUS = 1;  // MCHAP_UNIT_*
-constexpr int META_I_NDICT = 2;   // distinct values of the unit's table (0: more than DICT_MAX, no coded table)
-constexpr int META_I_FLAT = 3;    // 1: every entry of the unit's table (existing alleles) is a gap -- a sample without reads
-                                  // at the locus, which the reference samples all the same (assemble/mcmc.py:132-137): the
-                                  // likelihood of every genotype is then the same number
-constexpr int META_I_W01 = 4;     // 1: every read weight of the unit is 0 or 1 (no counts of de-duplicated rows): the lanes take ONE
-                                  // logarithm per group of up to four reads (read_log_sum, read_log.hpp); tuning flag 1048576: never
-constexpr int META_I_COLS = 5;    // then [M]: column (j * A) of sampled position jj ; then [M]: n_alleles
-__host__ __device__ inline int meta_i_stride(int max_pos) { return 5 + 2 * max_pos; }
-// SpecLds::ndict and its like hold the dictionary size with the unit's META_I_W01 in the top bit
-constexpr uint16_t ND_W01 = 0x8000u;
-__host__ __device__ inline int nd_count(uint16_t x) { return (int)(x & 0x7FFFu); }
-__host__ __device__ inline bool nd_w01(uint16_t x) { return (x & ND_W01) != 0; }
-// Coded read table (speculative sampler): a unit's table usually holds a few dozen distinct probabilities
-// (one per base quality, its error share, 1.0 for gaps), so it is also stored as uint8 codes into a per-unit
-// dictionary of float64 values: lossless, 8x smaller, and what the likelihood evaluation then streams stays in L2.
-constexpr int DICT_MAX = 128;  // entries kept per unit (LDS of the sampler: 1 KB per chain)
-constexpr int DICT_HASH = 512;   // open-addressing slots of the prepare pass's LDS set (at most DICT_MAX = 128 are taken)
-// doubles: [0] luh, [1..] prior table (2K+5), then dist [M*A]
-__host__ __device__ inline int meta_f_prior(int) { return 1; }
-__host__ __device__ inline int meta_f_dist(int max_ploidy) { return 1 + 2 * max_ploidy + 5; }
-__host__ __device__ inline int meta_f_stride(int max_ploidy, int max_pos, int max_allele) {
-  return 1 + 2 * max_ploidy + 5 + max_pos * max_allele;
-}
-
-struct SimtParams {
-  DenovoParams d;
-  // workspace carved by the host
-  double *rt;        // [U][max_ma][rpad]
-  double *cntw;      // [U][rpad]
-  uint8_t *codes;    // [U][max_ma][64][cstride]: code of read lane + 64 i at byte i of the lane's group
-  double *dict;      // [U][DICT_MAX]
-  double *gbp;       // [U * chains][max_ploidy][rpad] haplotype products of the chains' current genotypes for read chunks >= 4, or null
-  int32_t *meta_i;   // [U][meta_i_stride]
-  double *meta_f;    // [U][meta_f_stride]
-  int n_units;
-  int max_pos, max_allele, max_ploidy;
-  int max_ma;        // max over units of n_pos * max_allele
-  int max_ugens_pad; // doubles reserved for the SNV posterior scratch of the prepare pass
-  int prep_rows_off; // byte offset of the prepare pass's per-position row staging in its LDS
-  int cstride;       // bytes per lane and row of the coded table: rpad / 64 rounded up to 1, 2 or a multiple of 4
-  int flags;         // debugging: bit 0 no mutation memo, bit 1 no interval memo (MCHAP_HIP_FLAGS); bit 30 below
-  // steady-state pipeline (denovo_lane_kernel.hpp): per-chain hand-over records and threshold tables
-  void *lane_state;  // [U * chains] LaneState
-  void *lane_memo;   // [U * chains][2][tri(max_pos)] uint32
-  // phased sampler (kernel 5: denovo_spec_kernel<K, G, true> in phases + denovo_coast_kernel): hand-over records
-  void *pipe_state;           // [U * chains] PipeState
-  double *pipe_memo;          // [U * chains][2][tri(max_pos)] total move probabilities of the interval steps
-  const int32_t *pipe_list;   // chains of this launch (nullptr: all of them, in order)
-  const int32_t *pipe_count;  // their number, on the device (nullptr: all)
-  int32_t *pipe_out;          // coasting kernel: the chains it hands back, appended in any order
-  int32_t *pipe_out_count;
-  int pipe_iters;             // compound steps per chain in this launch (<= 0: to the end)
-  int pipe_iters_max;         // ... which a wave extends to while one of its chains is not settled (PIPE_EXPORT)
-  int pipe_mode;              // PIPE_RESUME | PIPE_EXPORT | PIPE_FILLONLY
-  int pipe_parts;             // wavefronts a short list of chains may spread the completion of one chain's tables over
-  int bp_cache;               // speculative sampler with one chain per wave: base-product cache carved after its LDS
-  int fill_lt, fill_kw;       // denovo_fill_kernel: lanes per tile of the read table, words kept per distinct request
-  int tw_lds;                 // denovo_spec_kernel<.., TW>: bytes of one wavefront's LDS layout behind the workgroup's exchange area
-  int word_bits;              // bits of a packed haplotype word of this launch's sampler: 0 / 64, or 128 (denovo_simt_kernel<0, u128>)
-  uint64_t cache_epoch;       // speculative / phased sampler: this call's epoch << 33, OR-ed into every likelihood-cache tag (0: the
-                              // caches were cleared for this call instead): entries of earlier calls never match, nothing is cleared
-  uint64_t *ctx;              // phased sampler, resumed chains: [U * chains][ctx_n][spec_ctx_words] decision contexts per genotype
-  int ctx_n;                  // (denovo_spec_kernel.hpp "decision contexts"), or null / 0
-};
-constexpr int PIPE_RESUME = 1;  // start from the chains' PipeState records
-constexpr int PIPE_EXPORT = 2;  // at the end: complete the interval memo of the current genotype, write the records
-// Completing a chain's tables is a few hundred likelihood evaluations served one after the other by its wavefront.
-// When a launch holds few chains (a list of handed-back chains; a small batch of a big shape) the chip is empty
-// and that latency is all there is: the exporting launch then leaves the tables as they are, and a PIPE_FILLONLY
-// launch follows in which pipe_parts_eff() wavefronts per chain each complete every pipe_parts_eff()-th unknown entry
-// (no steps, no records; the chain's likelihood cache is not used: the wavefronts would race on it).
-constexpr int PIPE_FILLONLY = 4;
-constexpr int PIPE_NOFILL = 8;  // PIPE_EXPORT without the table completion: denovo_fill_kernel (one lane per request) follows
-constexpr int PIPE_FILL_SLOTS = 1024;  // wavefront slots such a launch may occupy (one per SIMD: beyond that the chip is busy anyway)
-__host__ __device__ inline int pipe_parts_eff(int n_list, int parts) {
-  if (parts <= 1 || n_list <= 0) return 1;
-  const int pe = PIPE_FILL_SLOTS / n_list;
-  return pe < 1 ? 1 : (pe > parts ? parts : pe);
-}
-// hand-over record of a chain between the launches of the phased sampler
-struct PipeState {
-  uint64_t g[8];     // haplotype words in the chain's own (unsorted) order
-  double llk;
-  uint64_t ctr;      // next draw of the chain's stream
-  double mlo, mhi;   // mutation step: no move while every uniform is in [mlo, mhi)
-  int32_t step;      // MCMC steps done (== steps: finished, or stopped by an error status)
-  int32_t mvalid;
-  uint64_t pad[3];
-};
-static_assert(sizeof(PipeState) == 128, "PipeState layout");
-constexpr int SIMT_FLAG_PREP_GLOBAL = 1 << 30;  // table too large for the prepare pass's LDS copy
-
-// ---------------------------------------------------------------------------------------------------------
-// prepare: grid = units, block = 64
-// ---------------------------------------------------------------------------------------------------------
-#ifndef MCHAP_PREP_WPE
-#define MCHAP_PREP_WPE 4  // waves per SIMD the prepare pass is compiled for (it is latency-bound: one wave per unit)
-#endif
-template <int RPL>
-__global__ __launch_bounds__(64, MCHAP_PREP_WPE) void denovo_prepare_kernel(const SimtParams P) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  const DenovoParams &D = P.d;
-  const int u = blockIdx.x;
-  const mchap_unit U = D.units[u];
-  const int lane = threadIdx.x;
-  const int R = U.n_reads, M0 = U.n_pos, A = U.max_allele, K = U.ploidy;
-  const int rpad = D.rpad;
-  const int MA = M0 * A;
-  double *rt = P.rt + (size_t)u * P.max_ma * rpad;
-  // [MA][rpad] copy for the homozygous fix: in LDS when it fits, else the global table itself (every lane only
-  // re-reads the reads r = lane + 64 i it stored, so program order makes its own stores visible)
-  const bool in_lds = !(P.flags & SIMT_FLAG_PREP_GLOBAL);
-  double *rl = in_lds ? reinterpret_cast<double *>(smem) : rt;
-  double *lp = reinterpret_cast<double *>(smem) + (in_lds ? (size_t)MA * rpad : 0);  // snv posterior scratch
-  const double *gr = D.reads ? D.reads + U.reads_off : nullptr;
-  const int8_t *nal0 = D.n_alleles + U.nalleles_off;
-  // entry (r, q = j * A + a) of the unit's probability tensor: read from it, or formed from the allele calls as
-  // encoding/integer/transcode.py:16-77 does (called allele p, the others (1 - p) / 3, NaN for a gap, then 0 for
-  // alleles the position does not have)
-  auto rawv = [&](int r, int q) -> double {
-    if (gr) return gr[(size_t)r * MA + q];
-    const int j = q / A, a = q - j * A;
-    if (a >= nal0[j]) return 0.0;
-    const size_t e = (size_t)U.reads_off + (size_t)r * M0 + j;
-    const int call = D.calls[e];
-    if (call < 0) return NAN;
-    int qi = D.quals ? (int)D.quals[e] : 0;
-    qi = qi < 0 ? 0 : (qi >= D.qual_prob_len ? D.qual_prob_len - 1 : qi);
-    const double pc = D.qual_prob[qi];
-    return a == call ? pc : (1.0 - pc) / 3.0;
-  };
-  double *cw = P.cntw + (size_t)u * rpad;
-  int32_t *mi = P.meta_i + (size_t)u * meta_i_stride(P.max_pos);
-  double *mf = P.meta_f + (size_t)u * meta_f_stride(P.max_ploidy, P.max_pos, P.max_allele);
-
-  bool all_gaps = true;  // every factor a likelihood can read is 1.0
-  for (int r = lane; r < rpad; r += WAVE) {
-    // eight entries of the read's row at a time: the loads are independent and issued together (the stores that
-    // follow could alias them as far as the compiler knows)
-    for (int q0 = 0; q0 < MA; q0 += 8) {
-      double v[8];
-#pragma unroll
-      for (int k = 0; k < 8; k++) v[k] = (r < R && q0 + k < MA) ? rawv(r, q0 + k) : 1.0;
-#pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const int q = q0 + k;
-        if (q < MA) {
-          const double x = isnan(v[k]) ? 1.0 : v[k];
-          if (in_lds) rl[(size_t)q * rpad + r] = x;
-          rt[(size_t)q * rpad + r] = x;
-          if (q % A < (int)nal0[q / A]) all_gaps = all_gaps && (x == 1.0);
-        }
-      }
-    }
-  }
-  {
-    const bool flat = __ballot(!all_gaps) == 0ull;
-    if (lane == 0) mi[META_I_FLAT] = flat ? 1 : 0;
-  }
-  double cnt[RPL];
-#pragma unroll
-  for (int i = 0; i < RPL; i++) {
-    const int r = lane + WAVE * i;
-    cnt[i] = (r < R) ? (U.counts_off >= 0 ? (double)D.counts[U.counts_off + r] : 1.0) : 0.0;
-    cw[r] = cnt[i];
-  }
-  {
-    bool w01 = true;
-#pragma unroll
-    for (int i = 0; i < RPL; i++) w01 = w01 && (cnt[i] == 0.0 || cnt[i] == 1.0);
-    const bool all01 = __ballot(!w01) == 0ull;
-    if (lane == 0) mi[META_I_W01] = (all01 && !(P.flags & (1 << 20))) ? 1 : 0;
-  }
-  __syncthreads();
-  // ---- dictionary + coded table ----
-  {
-    unsigned long long *hkeys = reinterpret_cast<unsigned long long *>(lp + P.max_ugens_pad);  // [DICT_HASH]
-    uint16_t *hcode = reinterpret_cast<uint16_t *>(hkeys + DICT_HASH);                         // [DICT_HASH]
-    int *ndist = reinterpret_cast<int *>(hcode + DICT_HASH);
-    const unsigned long long EMPTY = ~0ull;  // a NaN pattern: table entries are never NaN
-    for (int i = lane; i < DICT_HASH; i += WAVE) hkeys[i] = EMPTY;
-    if (lane == 0) *ndist = 0;
-    __syncthreads();
-    const int RPLT = rpad / WAVE;
-    for (int q = 0; q < MA; q++) {
-      // the lane's RPL values of this row: loaded together (one memory round trip per row, not one per value)
-      for (int i0 = 0; i0 < RPL; i0 += 4) {
-      unsigned long long keys[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) keys[k] = (unsigned long long)__double_as_longlong(rt[(size_t)q * rpad + lane + WAVE * min(i0 + k, RPL - 1)]);
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        if (i0 + k >= RPL) break;
-        const unsigned long long key = keys[k];
-        unsigned slot = (unsigned)(mix64(key) & (DICT_HASH - 1));
-        while (*(volatile int *)ndist <= DICT_MAX) {
-          // plain read first: most entries repeat a value that is already in the set (same-address LDS atomics of a
-          // whole wavefront serialise)
-          unsigned long long old = *(volatile unsigned long long *)&hkeys[slot];
-          if (old == EMPTY) {
-            old = atomicCAS(&hkeys[slot], EMPTY, key);
-            if (old == EMPTY) atomicAdd(ndist, 1);
-          }
-          if (old == EMPTY || old == key) break;
-          slot = (slot + 1) & (DICT_HASH - 1);
-        }
-      }
-      }
-    }
-    __syncthreads();
-    const int nd = *ndist;
-    uint8_t *ct = P.codes + (size_t)u * P.max_ma * WAVE * P.cstride;
-    double *dict = P.dict + (size_t)u * DICT_MAX;
-    if (nd <= DICT_MAX) {
-      int base = 0;
-      for (int s0 = 0; s0 < DICT_HASH; s0 += WAVE) {
-        const unsigned long long key = hkeys[s0 + lane];
-        const bool occ = key != EMPTY;
-        const unsigned long long m = __ballot(occ);
-        const int code = base + __popcll(m & ((1ull << lane) - 1ull));
-        if (occ) {
-          hcode[s0 + lane] = (uint16_t)code;
-          dict[code] = __longlong_as_double((long long)key);
-        }
-        base += __popcll(m);
-      }
-      __syncthreads();
-      for (int q = 0; q < MA; q++) {
-        for (int i0 = 0; i0 < RPL; i0 += 4) {
-          unsigned long long keys[4];
-#pragma unroll
-          for (int k = 0; k < 4; k++) keys[k] = (unsigned long long)__double_as_longlong(rt[(size_t)q * rpad + lane + WAVE * min(i0 + k, RPL - 1)]);
-          uint32_t packed = 0;
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            if (i0 + k >= RPL) break;
-            const unsigned long long key = keys[k];
-            unsigned slot = (unsigned)(mix64(key) & (DICT_HASH - 1));
-            while (hkeys[slot] != key) slot = (slot + 1) & (DICT_HASH - 1);
-            if (RPL > 2) packed |= (uint32_t)(uint8_t)hcode[slot] << (8 * k);
-            else ct[((size_t)q * WAVE + lane) * P.cstride + i0 + k] = (uint8_t)hcode[slot];
-          }
-          // (cstride is a multiple of 4 beyond two chunks: one aligned 4-byte store instead of four byte stores;
-          // bytes past the unit's chunks are padding the sampler never reads)
-          if (RPL > 2) *reinterpret_cast<uint32_t *>(ct + ((size_t)q * WAVE + lane) * P.cstride + i0) = packed;
-        }
-      }
-    }
-    if (lane == 0) mi[META_I_NDICT] = nd <= DICT_MAX ? nd : 0;
-  }
-  const int8_t *nalleles = D.n_alleles + U.nalleles_off;
-  // homozygous fix (assemble/mcmc.py:168-182, 494-541; snpcalling.py:14-70)
-  int Mh = 0;
-  double luh = 0.0;
-  const bool pow2_ploidy = (K & (K - 1)) == 0;
-  const double inv_ploidy = 1.0 / (double)K;
-  // The SNV prior (snv_log_prior: calling/prior.py:116-179 with flat frequencies) needs lgamma(dose + 1) and, with
-  // inbreeding, lgamma(dose + alpha_n), lgamma(alpha_n) and the normaliser for every allele count n: a few dozen
-  // distinct values per unit.  Every lane used to recompute K + 1 of them per genotype (200 calls of ~400
-  // instructions per unit: 60 % of this pass); now each value is formed once, one per lane.
-  constexpr int KP = MCHAP_MAX_PLOIDY_DENOVO;  // (the prepare pass serves every sampler: ploidies up to 15, packs of sixteen nibbles)
-  __shared__ double s_lg1[KP + 1];                              // lgamma(d + 1)
-  __shared__ double s_lga[(MCHAP_MAX_ALLELE + 1) * (KP + 1)];   // lgamma(d + alpha_n), d >= 1
-  __shared__ double s_lgb[MCHAP_MAX_ALLELE + 1], s_left[MCHAP_MAX_ALLELE + 1];  // lgamma(alpha_n); normaliser
-  const double Fp = U.inbreeding;
-  const bool with_prior = !isnan(Fp);
-  if (with_prior) {
-    for (int d = lane; d <= K; d += WAVE) s_lg1[d] = lgamma((double)d + 1.0);
-    if (Fp != 0.0) {
-      for (int e = lane; e < (A + 1) * (K + 1); e += WAVE) {
-        const int n = e / (K + 1), d = e % (K + 1);
-        if (n >= 1 && d >= 1) s_lga[n * (KP + 1) + d] = lgamma((double)d + (1.0 / (double)n) * ((1.0 - Fp) / Fp));
-      }
-      for (int n = 1 + lane; n <= A; n += WAVE) {
-        const double alpha = (1.0 / (double)n) * ((1.0 - Fp) / Fp);
-        const double sum_alphas = alpha * (double)n;
-        s_lgb[n] = lgamma(alpha);
-        s_left[n] = (lgamma((double)K + 1.0) + lgamma(sum_alphas)) - lgamma((double)K + sum_alphas);
-      }
-    }
-    __syncthreads();
-  }
-  // snv_log_prior(g, K, n, F) from the tables: same arguments to the same lgamma, same order of the sums
-  auto snv_prior = [&](uint64_t g, int n) -> double {
-    int dose[KP];
-    for (int i = 0; i < K; i++) dose[i] = 0;
-    for (int i = 0; i < K; i++) {
-      int j = 0;
-      while (nib(g, i) != nib(g, j)) j++;
-      dose[j] += 1;
-    }
-    if (Fp == 0.0) {
-      double den = 0.0;
-      for (int i = 0; i < K; i++) den += s_lg1[dose[i]];
-      return (s_lg1[K] - den) - (double)K * c_ln[n];
-    }
-    double prod = 0.0;
-    for (int i = 0; i < K; i++)
-      if (dose[i] > 0) prod += s_lga[n * (KP + 1) + dose[i]] - (s_lg1[dose[i]] + s_lgb[n]);
-    return s_left[n] + prod;
-  };
-  // without the LDS copy of the whole table, the A rows of the current position are staged in LDS (each lane its own
-  // reads): the genotype loop below re-reads them K times per genotype
-  double *pl = reinterpret_cast<double *>(smem + P.prep_rows_off);  // [A][rpad]
-  for (int j = 0; j < M0; j++) {
-    const int n = nalleles[j];
-    const int u_gens = snv_genotypes(n, K);
-    const double *rowp = rl + (size_t)(j * A) * rpad;
-    if (!in_lds) {
-      for (int a = 0; a < A; a++)
-#pragma unroll
-        for (int i = 0; i < RPL; i++) pl[(size_t)a * rpad + lane + WAVE * i] = rt[(size_t)(j * A + a) * rpad + lane + WAVE * i];
-      rowp = pl;
-    }
-    uint64_t g = 0;  // the SNV genotype's alleles, one nibble each
-    for (int q = 0; q < u_gens; q++) {
-      double lprior = 0.0;
-      if (with_prior) lprior = snv_prior(g, n);
-      double s = 0.0;
-#pragma unroll
-      for (int i = 0; i < RPL; i++) {
-        double rp = 0.0;
-        // x / K (snpcalling.py / likelihood.py:61); for K = 2, 4, 8 the product with 1 / K is the same double
-        if (pow2_ploidy) {
-          for (int h = 0; h < K; h++) rp += rowp[(size_t)nib(g, h) * rpad + lane + WAVE * i] * inv_ploidy;
-        } else {
-          for (int h = 0; h < K; h++) rp += rowp[(size_t)nib(g, h) * rpad + lane + WAVE * i] / (double)K;
-        }
-        s += read_log(rp) * cnt[i];
-      }
-      const double llk = wave_sum(s);
-      lp[q] = lprior + llk;
-      g = increment_snv_genotype(g, K);
-    }
-    double acc = lp[0];
-    for (int q = 1; q < u_gens; q++) acc = add_log_prob(acc, lp[q]);
-    int fixed_allele = -1;
-    for (int a = 0; a < n; a++) {
-      int idx = 0;
-      for (int i = 0; i < K; i++) idx += (a == 0) ? 0 : snv_genotypes(a, i + 1);
-      if (exp(lp[idx] - acc) >= D.fix_hom) fixed_allele = a;
-    }
-    if (lane == 0) D.fixed[U.fixed_off + j] = (int8_t)fixed_allele;
-    if (fixed_allele < 0) {
-      if (lane == 0) {
-        mi[META_I_COLS + Mh] = j * A;
-        mi[META_I_COLS + P.max_pos + Mh] = n;
-      }
-      luh += c_ln[n];  // assemble/mcmc.py:294
-      Mh++;
-    }
-  }
-  const int bits = allele_bits(A);
-  int status = MCHAP_UNIT_OK;
-  if (Mh == 0) status = MCHAP_UNIT_ALL_FIXED;
-  else if (Mh * bits > (P.word_bits ? P.word_bits : 64)) status = MCHAP_ERR_LIMIT;
-  else if (U.initial_off >= 0 && U.initial_n_het != Mh) status = MCHAP_UNIT_BAD_INITIAL;  // assemble/mcmc.py:207
-  if (lane == 0) {
-    mi[META_I_MH] = Mh;
-    mi[META_I_STATUS] = status;
-    D.status[u] = status;
-    mf[0] = luh;
-  }
-  if (status != MCHAP_UNIT_OK) {
-    if (status == MCHAP_UNIT_ALL_FIXED) {
-      // assemble/mcmc.py:189-199: constant trace, NaN llks
-      const size_t tb = U.trace_off, lb = U.llk_off;
-      const int S = D.steps, C_ = D.chains;
-      for (int i = lane; i < C_ * S * K; i += WAVE) D.trace[tb + i] = 0ull;
-      for (int i = lane; i < C_ * S; i += WAVE) D.llks[lb + i] = NAN;
-    }
-    return;
-  }
-  // prior tables (assemble/prior.py:39-112), same layout as Chain::prior_tab
-  if (!isnan(U.inbreeding) && lane == 0) {
-    double *t = mf + meta_f_prior(0);
-    const double F = U.inbreeding;
-    for (int d = 0; d <= K; d++) t[K + 1 + d] = lgamma((double)d + 1.0);
-    t[2 * K + 3] = lgamma((double)K + 1.0);
-    t[2 * K + 4] = (double)K * luh;
-    if (F != 0.0) {
-      const double log_disp = log((1.0 - F) / F) - luh;
-      const double disp = exp(log_disp);
-      const double sum_disp = exp(log_disp + luh);
-      const double lg_disp = lgamma(disp);
-      t[0] = 0.0;
-      for (int d = 1; d <= K; d++) t[d] = lgamma((double)d + disp) - (lgamma((double)d + 1.0) + lg_disp);
-      t[2 * K + 2] = (lgamma((double)K + 1.0) + lgamma(sum_disp)) - lgamma((double)K + sum_disp);
-    }
-  }
-  // _read_mean_dist (assemble/mcmc.py:455-491) over the sampled positions, from the raw tensor
-  if (U.initial_off < 0) {
-    double *dist = mf + meta_f_dist(P.max_ploidy);
-    __syncthreads();
-    for (int jj = 0; jj < Mh; jj++) {
-      const int col = mi[META_I_COLS + jj];
-      int n_nonzero = 0;
-      uint32_t gapmask = 0;
-      double dv[MCHAP_MAX_ALLELE];
-      for (int a = 0; a < A; a++) {
-        double tot = 0.0;
-        int n_ok = 0, n_nz = 0;
-        for (int i0 = 0; i0 < RPL; i0 += 4) {  // four of the lane's reads at a time: their loads are independent
-          double v4[4];
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            const int r = lane + WAVE * (i0 + k);
-            v4[k] = (i0 + k < RPL && r < R) ? rawv(r, col + a) : 0.0;
-          }
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            const int r = lane + WAVE * (i0 + k);
-            if (i0 + k < RPL && r < R) {
-              const double v = v4[k];
-              if (!isnan(v)) {
-                tot += v;
-                n_ok++;
-              }
-              if (!(v == 0.0)) n_nz++;
-            }
-          }
-        }
-        tot = wave_sum(tot);
-        n_ok = wave_sum_i(n_ok);
-        n_nz = wave_sum_i(n_nz);
-        if (n_ok == 0) {
-          gapmask |= 1u << a;
-          dv[a] = 1.0;
-          n_nonzero++;
-        } else {
-          dv[a] = tot / (double)n_ok;
-          if (n_nz > 0) n_nonzero++;
-        }
-      }
-      for (int a = 0; a < A; a++)
-        if (gapmask & (1u << a)) dv[a] = 1.0 / (double)n_nonzero;
-      double s = 0.0;
-      for (int a = 1; a < A; a++) s += dv[a];
-      s = (A > 1) ? dv[0] + s : dv[0];
-      if (lane == 0)
-        for (int a = 0; a < A; a++) dist[jj * A + a] = dv[a] / s;
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // sampler: one lane per chain
@@ -739,29 +292,6 @@ __device__ __forceinline__ uint64_t lane_genotype_tag(const SimtLdsT<W> &S, cons
   }
   return (t << 1) | 1ull;
 }
-
-#if defined(MCHAP_STATS) || defined(MCHAP_PHASES)
-constexpr int N_STATS = 64;  // [0..23] event counters, [24..35] phase timers of the steps, [36..47] ... of the table completion, [48..55] sub-timers of the steps
-static __device__ unsigned long long g_stats[N_STATS];
-#endif
-#ifdef MCHAP_STATS
-#define STAT_ADD(i, pred)                                                         \
-  do {                                                                            \
-    const int n_ = __popcll(__ballot(pred));                                      \
-    if (n_ && (threadIdx.x & 63) == 0) atomicAdd(&g_stats[i], (unsigned long long)n_); \
-  } while (0)
-#define STAT_WAVE(i, n)                                                                     \
-  do {                                                                                      \
-    if ((threadIdx.x & 63) == 0) atomicAdd(&g_stats[i], (unsigned long long)(n));           \
-  } while (0)
-#else
-#define STAT_ADD(i, pred) \
-  do {                    \
-  } while (0)
-#define STAT_WAVE(i, n) \
-  do {                  \
-  } while (0)
-#endif
 
 // likelihood of the lane's proposal S.pw[.][lane] (where need): cache probe, co-operative evaluation on a miss.
 // The per-chain table is 4-way set associative (one 64-byte line per set): a hit in way k > 0 moves the entry one

@@ -21,11 +21,11 @@
 // reuse of the current genotype's haplotype products by the requests of one chain.
 //
 // Launch: one wavefront per 64/G chains, all units of a launch share the ploidy KT; prepare kernel and workspace
-// as for the lanes-over-chains kernel (denovo_simt_kernel.hpp).  Same traces as the other two kernels.
+// from the prepare pass (denovo_prepare_kernel.hpp, denovo_common.hpp).  Same traces as the other kernels.
 #pragma once
 #include <type_traits>
 
-#include "denovo_simt_kernel.hpp"
+#include "denovo_common.hpp"
 
 #ifdef MCHAP_MASK_PADDING
 #define MCHAP_PAD_LANE(x) (x)
@@ -76,23 +76,6 @@ namespace mchap {
 constexpr int SPEC_MAX_IV = 64;  // intervals per structural compound step (<= n_pos)
 constexpr int SPEC_TB = MCHAP_SPEC_TB;    // trace records per flush: K = 4 -> one 128-byte line of words + 32 bytes of llks
 constexpr int SPEC_LN = 72;   // log tables: counts up to K(K-1) <= 56
-constexpr int SPEC_DRAWS_MAX = 384;  // draws of the current stream staged in LDS per group (Philox blocks in parallel)
-__host__ __device__ inline int spec_draws(int K, int Mmax) {
-  int d = 2 * K * Mmax - 1;
-  if (d < 3 * Mmax + 2) d = 3 * Mmax + 2;
-  d = (d + 1) & ~1;
-  return d < SPEC_DRAWS_MAX ? d : SPEC_DRAWS_MAX;
-}
-
-// LDS pointers carry their address space so that every access is a ds_* instruction (a pointer stored in a struct
-// otherwise degrades to a generic "flat" access)
-#define LDSP(T) __attribute__((address_space(3))) T *
-#define GLBP(T) __attribute__((address_space(1))) T *
-template <class T>
-__device__ __forceinline__ LDSP(T) lds_cast(void *p) {
-  return (LDSP(T))p;
-}
-
 // The unit's coded table and read weights: in HBM / L2 (LT = false, the speculative kernel) or copied into the wave's LDS
 // (LT = true, the settling kernel of denovo_lane_kernel.hpp, whose evaluations are then free of memory latency).
 template <bool LT>
@@ -178,9 +161,6 @@ struct SpecLds {
 };
 
 // interval-step memo (see spec_structural): only for a single temperature and while it stays small
-// entries of one interval-step memo table: intervals (start, stop) with 0 <= start < stop <= Mmax, triangular
-__host__ __device__ inline int spec_memo_entries(int Mmax) { return Mmax * (Mmax + 1) / 2; }
-__host__ __device__ inline int spec_memo_index(int start, int stop) { return stop * (stop - 1) / 2 + start; }
 __host__ __device__ inline size_t spec_memo_bytes(int Mmax, int T, int G) {
   const size_t per_group = (size_t)2 * spec_memo_entries(Mmax) * 8;
   if (T != 1 || per_group > 16 * 1024) return 0;
@@ -209,13 +189,6 @@ __host__ __device__ inline int spec_lc_entries(int bp_cache) { return (bp_cache 
 __device__ __forceinline__ uint32_t sct_off(uint32_t row) { return (row / 24u) * (uint32_t)(4 * WAVE * 8) + (row % 24u) * (uint32_t)WAVE; }
 // LDS of the base-product cache (SpecLds::bpc / bpt) of a one-chain-per-wave launch
 __host__ __device__ inline size_t spec_bp_cache_bytes(int K) { return (size_t)8 * K * 4 * 64 + (size_t)8 * (K + 1); }
-
-// dynamic LDS of denovo_coast_kernel<NW> (denovo_coast_kernel.hpp): a chain's two memo tables, its break distribution,
-// its sorted words, the wavefronts' first undecided steps
-constexpr int COAST_NW_LIST = 4;  // wavefronts per chain of a coasting launch over a list of handed-back chains
-__host__ __device__ inline size_t coast_lds_bytes(int Mmax) {
-  return (size_t)8 * (2 * spec_memo_entries(Mmax) + Mmax) + (size_t)8 * 12;
-}
 
 __host__ __device__ inline size_t spec_lds_bytes(int K, int Mmax, int Amax, int T, int G) {
   const int NG = 64 / G;
@@ -254,10 +227,7 @@ __host__ __device__ inline size_t spec_lds_bytes(int K, int Mmax, int Amax, int 
   return (b + 63) & ~(size_t)63;
 }
 
-// stateless Philox draws of a stream (same contract as Rng in philox.hpp)
-struct Stream {
-  uint32_t k0, k1, c2, c3;
-};
+// draw n of a Stream (denovo_common.hpp)
 __device__ __forceinline__ void stream_words(const Stream &s, uint64_t n, uint32_t &a, uint32_t &b) {
   uint32_t o[4];
   const uint64_t blk = n >> 1;
@@ -294,10 +264,6 @@ __device__ __forceinline__ void stage_draws(const Stream &s, uint64_t base, int 
     }
   }
 }
-__device__ __forceinline__ double draw_double(uint64_t w) {
-  return ((double)((uint32_t)w >> 5) * 67108864.0 + (double)((uint32_t)(w >> 32) >> 6)) * (1.0 / 9007199254740992.0);
-}
-__device__ __forceinline__ uint32_t draw_interval(uint64_t w, uint32_t max) { return __umulhi((uint32_t)w, max + 1u); }
 
 template <int G>
 __device__ __forceinline__ uint64_t grp_ballot(bool p, int gi) {
@@ -325,14 +291,6 @@ __device__ __forceinline__ double grp_max_f64(double v) {
   v = fmax(v, dpp_f64<0x122>(v));  // row_ror:2
   v = fmax(v, dpp_f64<0x121>(v));  // row_ror:1
   return v;
-}
-__device__ __forceinline__ void lds_sync() {
-#ifdef MCHAP_SYNC_BARRIER
-  __syncthreads();
-#else
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-#endif
 }
 
 // The K haplotype words of a genotype.  The helpers take it BY VALUE and the kernel copies the chain's words into

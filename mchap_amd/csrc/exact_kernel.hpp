@@ -8,7 +8,8 @@
 // (H <= 32) and equal ones broadcast.  Each lane then runs the reference's own sequential sum over reads for
 // its genotype; genotypes are visited in VCF order (index -> alleles by combinatorial unranking).
 #pragma once
-#include "denovo_kernel.hpp"
+#include "read_log.hpp"
+#include "wave_math.hpp"
 
 namespace mchap {
 

@@ -12,7 +12,9 @@
 #include <vector>
 
 #include "host_common.hpp"
-#include "denovo_kernel.hpp"
+#include "sampler_objects.hpp"
+#include "denovo_llk_kernel.hpp"
+#include "denovo_prepare_kernel.hpp"
 #include "denovo_simt_kernel.hpp"
 #include "denovo_spec_kernel.hpp"
 #include "denovo_fillw_kernel.hpp"
@@ -22,67 +24,19 @@
 #endif
 
 // ---- sampler objects ------------------------------------------------------------------------------------------
-// Every instantiation of a sampler kernel is its own object file (spec_inst.hip, simt_inst.hip, ...: they compile in
-// parallel) with two internal entry points: init (its copy of the constant log tables) and launch.
-#define SPEC_LIST(X) X(2, 16) X(2, 32) X(2, 64) X(3, 16) X(3, 32) X(3, 64) X(4, 16) X(4, 32) X(4, 64) X(5, 32) X(5, 64) X(6, 32) X(6, 64) X(7, 64) X(8, 64)
-// phased form: one chain per wavefront at every ploidy (the narrower groups were measured slower; they
-// stay in the test library so that the parity suite keeps covering hand-over with several chains per wave)
+// Every instantiation of a sampler kernel is its own object file with one descriptor; sampler_objects.hpp lists them.
 #ifdef MCHAP_TEST_KERNELS
-#define SPECP_LIST(X) X(2, 64) X(3, 64) X(4, 64) X(5, 64) X(6, 64) X(7, 64) X(8, 64) X(2, 16) X(3, 16) X(4, 16) X(4, 32) X(5, 32) X(6, 32)
+#define SAMPLER_OBJECTS(X) SPEC_LIST(X) SPECP_LIST(X) SPECS_LIST(X) SPECD_LIST(X) SIMT_LIST(X) FILLW_LIST(X) SPECP_TEST_LIST(X) FILL_LIST(X)
 #else
-#define SPECP_LIST(X) X(2, 64) X(3, 64) X(4, 64) X(5, 64) X(6, 64) X(7, 64) X(8, 64)
+#define SAMPLER_OBJECTS(X) SPEC_LIST(X) SPECP_LIST(X) SPECS_LIST(X) SPECD_LIST(X) SIMT_LIST(X) FILLW_LIST(X)
 #endif
-// the phased form with the side-by-side evaluation of shallow units compiled in (MCHAP_SPEC_SBS, denovo_spec_kernel.hpp)
-#define SPECS_LIST(X) X(2, 64) X(3, 64) X(4, 64) X(5, 64) X(6, 64) X(7, 64) X(8, 64)
-#define SIMT_LIST(X) X(0) X(2) X(4) X(6) X(8)
-#define V1_LIST(X) X(1) X(2) X(4) X(8) X(16)
-#define LANE_LIST(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-
-typedef int (*init_fn)(const double *, const double *);
-typedef int (*simt_launch_fn)(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
-#define DECL_LAUNCH(p, l, s) extern "C" int mchap_##p##_##l##_##s(const mchap::SimtParams *, unsigned, size_t, hipStream_t);
-#define DECL_OBJ(p, s) extern "C" int mchap_##p##_init_##s(const double *, const double *); DECL_LAUNCH(p, launch, s)
-#define DECL_SPEC(k, g) DECL_OBJ(spec, k##_##g)
-#define DECL_SPECP(k, g) DECL_OBJ(specp, k##_##g)
-// (the side-by-side and deep variants; and what only the instantiations with one chain per wavefront have: the launcher with
-// decision contexts per genotype of each phased variant, the speculative sampler's with a wavefront per replica of a ladder)
-#define DECL_SPECS(k, g) DECL_OBJ(specs, k##_##g) DECL_OBJ(specd, k##_##g) DECL_LAUNCH(spec, launchtw, k##_##g) \
-  DECL_LAUNCH(specp, launchc, k##_##g) DECL_LAUNCH(specs, launchc, k##_##g) DECL_LAUNCH(specd, launchc, k##_##g)
-#define DECL_SIMT(k) DECL_OBJ(simt, k)
-SPEC_LIST(DECL_SPEC)
-SPECP_LIST(DECL_SPECP)
-SPECS_LIST(DECL_SPECS)
-SIMT_LIST(DECL_SIMT)
-// ... and its instantiation with 128-bit haplotype words (simt_inst.hip -DSIMT_WIDE): the general fallback for wide targets
-DECL_OBJ(simt, w)
-extern "C" int mchap_coast_launch(const mchap::SimtParams *, unsigned, int, hipStream_t);
-// table completion of the phased sampler, one workgroup per chain and one wavefront per request (denovo_fillw_kernel.hpp): shipped
-#define FILLW_LIST(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#define DECL_FILLW(k) DECL_OBJ(fillw, k)
-FILLW_LIST(DECL_FILLW)
+#define DECL_OBJ(kind, k, g) extern "C" const mchap::SpecInst SAMPLER_OBJ(kind, k, g);
+SAMPLER_OBJECTS(DECL_OBJ)
 #ifdef MCHAP_TEST_KERNELS
-#define FILL_LIST(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
-#define DECL_FILL(k) DECL_OBJ(fill, k)
-FILL_LIST(DECL_FILL)
-#define DECL_V1(r)                                                \
-  extern "C" int mchap_v1_init_##r(const double *, const double *); \
-  extern "C" int mchap_v1_launch_##r(const mchap::DenovoParams *, unsigned, unsigned, unsigned, size_t, hipStream_t);
-#define DECL_LANE(k)                                                \
-  extern "C" int mchap_lane_init_##k(const double *, const double *); \
-  extern "C" int mchap_lane_launch_##k(const mchap::SimtParams *, int, int, unsigned, size_t, hipStream_t);
+#define DECL_V1(r) extern "C" const mchap::V1Inst V1_OBJ(r);
+#define DECL_LANE(k) extern "C" const mchap::LaneInst LANE_OBJ(k);
 V1_LIST(DECL_V1)
 LANE_LIST(DECL_LANE)
-#endif
-#if defined(MCHAP_STATS) || defined(MCHAP_PHASES)
-#define DECL_SPEC_STATS(k, g) extern "C" int mchap_spec_stats_##k##_##g(unsigned long long *, int);
-#define DECL_SPECP_STATS(k, g) extern "C" int mchap_specp_stats_##k##_##g(unsigned long long *, int);
-#define DECL_SPECS_STATS(k, g) extern "C" int mchap_specs_stats_##k##_##g(unsigned long long *, int); extern "C" int mchap_specd_stats_##k##_##g(unsigned long long *, int);
-SPEC_LIST(DECL_SPEC_STATS)
-SPECP_LIST(DECL_SPECP_STATS)
-SPECS_LIST(DECL_SPECS_STATS)
-#ifdef MCHAP_TEST_KERNELS
-extern "C" int mchap_lane_stats_4(unsigned long long *, int);
-#endif
 #endif
 
 namespace {
@@ -136,30 +90,31 @@ struct SamplerTimer {
   }
 };
 
-// The instantiations of the speculative sampler (kernel 3) and of the phased form's three variants (kernel 5), one table
-enum Variant { VAR_SPEC, VAR_PHASED, VAR_SBS, VAR_DEEP };
+// The sampler objects of this library, one table (sampler_objects.hpp): the speculative sampler (kernel 3), the phased form's three
+// variants (kernel 5), the lane-per-chain sampler (kernel 2) and the table completions
+using mchap::simt_launch_fn;
+using mchap::SpecInst;
+using mchap::VAR_DEEP;
+using mchap::VAR_FILL;
+using mchap::VAR_FILLW;
+using mchap::VAR_PHASED;
+using mchap::VAR_SBS;
+using mchap::VAR_SIMT;
+using mchap::VAR_SPEC;
 const char *const VARIANT_NAME[] = {"speculative sampler", "phased sampler", "phased sampler (side by side)", "phased sampler (deep)"};
-struct SpecInst {
-  int variant, K, G;
-  init_fn init;
-  simt_launch_fn launch;
-  simt_launch_fn launch_c;   // with decision contexts per genotype (phased, one chain per wavefront), else null
-  simt_launch_fn launch_tw;  // a wavefront per replica of a temperature ladder (speculative, one chain per wavefront), else null
-};
-#define LAUNCH_16(p, l, k) nullptr
-#define LAUNCH_32(p, l, k) nullptr
-#define LAUNCH_64(p, l, k) mchap_##p##_##l##_##k##_64
-#define ROW(v, p, k, g, c, tw) {v, k, g, mchap_##p##_init_##k##_##g, mchap_##p##_launch_##k##_##g, c, tw},
-#define ROW_SPEC(k, g) ROW(VAR_SPEC, spec, k, g, nullptr, LAUNCH_##g(spec, launchtw, k))
-#define ROW_SPECP(k, g) ROW(VAR_PHASED, specp, k, g, LAUNCH_##g(specp, launchc, k), nullptr)
-#define ROW_SPECS(k, g) ROW(VAR_SBS, specs, k, g, LAUNCH_##g(specs, launchc, k), nullptr)
-#define ROW_SPECD(k, g) ROW(VAR_DEEP, specd, k, g, LAUNCH_##g(specd, launchc, k), nullptr)
-const SpecInst SPEC_INSTS[] = {SPEC_LIST(ROW_SPEC) SPECP_LIST(ROW_SPECP) SPECS_LIST(ROW_SPECS) SPECS_LIST(ROW_SPECD)};
+#define ROW_OBJ(kind, k, g) &SAMPLER_OBJ(kind, k, g),
+const SpecInst *const SPEC_INSTS[] = {SAMPLER_OBJECTS(ROW_OBJ)};
 const SpecInst *find_inst(int variant, int K, int G) {
-  for (const SpecInst &i : SPEC_INSTS)
-    if (i.variant == variant && i.K == K && i.G == G) return &i;
+  for (const SpecInst *i : SPEC_INSTS)
+    if (i->variant == variant && i->K == K && i->G == G) return i;
   return nullptr;
 }
+#ifdef MCHAP_TEST_KERNELS
+#define ROW_V1(r) &V1_OBJ(r),
+#define ROW_LANE(k) &LANE_OBJ(k),
+const mchap::V1Inst *const V1_INSTS[] = {V1_LIST(ROW_V1)};
+const mchap::LaneInst *const LANE_INSTS[] = {LANE_LIST(ROW_LANE)};  // (ploidy K at [K - 1])
+#endif
 
 }  // namespace
 
@@ -178,22 +133,17 @@ int mchap::ensure_init() {
   }
   HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(mchap::c_ln), ln, sizeof(ln)));
   HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(mchap::c_ln_inv), ln_inv, sizeof(ln_inv)));
-  for (const SpecInst &i : SPEC_INSTS)
-    if (i.init(ln, ln_inv) != 0) return fail(MCHAP_ERR_HIP, "constant tables of the %s <%d, %d>", VARIANT_NAME[i.variant], i.K, i.G);
-  {
-#define ROW_SIMT_INIT(k) mchap_simt_init_##k,
-#define ROW_V1_INIT(r) mchap_v1_init_##r,
-#define ROW_LANE_INIT(k) mchap_lane_init_##k,
-#define ROW_FILL_INIT(k) mchap_fill_init_##k,
-#define ROW_FILLW_INIT(k) mchap_fillw_init_##k,
-    const init_fn inits[] = {SIMT_LIST(ROW_SIMT_INIT) mchap_simt_init_w, FILLW_LIST(ROW_FILLW_INIT)
-#ifdef MCHAP_TEST_KERNELS
-                                 FILL_LIST(ROW_FILL_INIT) V1_LIST(ROW_V1_INIT) LANE_LIST(ROW_LANE_INIT)
-#endif
-    };
-    for (init_fn f : inits)
-      if (f(ln, ln_inv) != 0) return fail(MCHAP_ERR_HIP, "constant tables of a sampler object");
+  for (const SpecInst *i : SPEC_INSTS) {
+    if (i->init(ln, ln_inv) == 0) continue;
+    if (i->variant <= VAR_DEEP) return fail(MCHAP_ERR_HIP, "constant tables of the %s <%d, %d>", VARIANT_NAME[i->variant], i->K, i->G);
+    return fail(MCHAP_ERR_HIP, "constant tables of a sampler object");
   }
+#ifdef MCHAP_TEST_KERNELS
+  for (const mchap::V1Inst *i : V1_INSTS)
+    if (i->init(ln, ln_inv) != 0) return fail(MCHAP_ERR_HIP, "constant tables of a sampler object");
+  for (const mchap::LaneInst *i : LANE_INSTS)
+    if (i->init(ln, ln_inv) != 0) return fail(MCHAP_ERR_HIP, "constant tables of a sampler object");
+#endif
   if (dev < 64) g_init_done[dev] = true;
   return MCHAP_OK;
 }
@@ -590,11 +540,12 @@ int launch_prepare(const mchap::SimtParams &P, int n_units, size_t lds_prep, hip
 
 int launch_simt(int KT, const mchap::SimtParams &P, int n_units, int chains, size_t lds_simt, void *timer, hipStream_t stream,
                 bool wide = false) {
-  simt_launch_fn launch = wide ? mchap_simt_launch_w :
-      KT == 2 ? mchap_simt_launch_2 : KT == 4 ? mchap_simt_launch_4 : KT == 6 ? mchap_simt_launch_6 : KT == 8 ? mchap_simt_launch_8 : mchap_simt_launch_0;
+  // the instantiation of the compile-time ploidy if there is one, else the one with a ploidy per lane; 128-bit words: that one only
+  const SpecInst *inst = wide ? find_inst(VAR_SIMT, 0, 128) : find_inst(VAR_SIMT, KT, 64);
+  if (!inst) inst = find_inst(VAR_SIMT, 0, 64);
   const long long n_chains = (long long)n_units * chains;
   SamplerTimer tm(timer, stream);
-  const int e = launch(&P, (unsigned)((n_chains + 63) / 64), lds_simt, stream);
+  const int e = inst->launch(&P, (unsigned)((n_chains + 63) / 64), lds_simt, stream);
   if (e != 0) return fail(MCHAP_ERR_HIP, "launch of denovo_simt_kernel<%d>: %s", KT, hipGetErrorString((hipError_t)e));
   return MCHAP_OK;
 }
@@ -637,8 +588,11 @@ int launch_spec(const Tune &T, int K, int G, const mchap::SimtParams &P, int n_u
 
 #ifdef MCHAP_TEST_KERNELS
 int launch_denovo(int rpl, const mchap::DenovoParams &P, int n_units, int chains, size_t lds, void *timer, hipStream_t stream) {
-  int (*launch)(const mchap::DenovoParams *, unsigned, unsigned, unsigned, size_t, hipStream_t) =
-      rpl == 1 ? mchap_v1_launch_1 : rpl == 2 ? mchap_v1_launch_2 : rpl == 4 ? mchap_v1_launch_4 : rpl == 8 ? mchap_v1_launch_8 : mchap_v1_launch_16;
+  // the instantiation with the batch's reads per lane; any other count runs on the one with 16
+  const mchap::V1Inst *inst = nullptr;
+  for (const mchap::V1Inst *i : V1_INSTS)
+    if (i->rpl == rpl || (!inst && i->rpl == 16)) inst = i;
+  auto launch = inst->launch;
   const int cpb = chains < mchap::CHAINS_PER_BLOCK ? chains : mchap::CHAINS_PER_BLOCK;
   SamplerTimer tm(timer, stream);
   const int e = launch(&P, (unsigned)n_units, (unsigned)((chains + cpb - 1) / cpb), (unsigned)(64 * cpb), lds, stream);
@@ -656,9 +610,7 @@ int lane_shift(int K, int max_pos, int max_allele, int tab_bytes, int rpad) {
 }
 
 int launch_lane(const Tune &T, int K, const mchap::SimtParams &P, int n_units, int chains, void *timer, hipStream_t stream) {
-#define ROW_LANE_LAUNCH(k) mchap_lane_launch_##k,
-  int (*const launches[])(const mchap::SimtParams *, int, int, unsigned, size_t, hipStream_t) = {LANE_LIST(ROW_LANE_LAUNCH)};
-  auto launch = launches[K - 1];
+  auto launch = LANE_INSTS[K - 1]->launch;
   const long long n_chains = (long long)n_units * chains;
   const int tab_bytes = P.max_ma * 64 * P.cstride;
   const int lsh = lane_shift(K, P.max_pos, P.max_allele, tab_bytes, P.d.rpad);
@@ -786,16 +738,14 @@ int launch_pipe(const Tune &T, int K, int G, mchap::SimtParams P, int n_units, i
     // (the instantiation: keyed by changed words / deep units: fillw_inst.hip; bits 8..: entries / 256 of the memo across chunks)
     P.fill_kw = (fillw_wide ? 1 : 0) | (P.gbp != nullptr ? 2 : 0) | ((fillw_memo / 256) << 8);
   }
-#define ROW_FILLW_LAUNCH(k) mchap_fillw_launch_##k,
-  const simt_launch_fn fillw_launches[] = {FILLW_LIST(ROW_FILLW_LAUNCH)};
+  const SpecInst *const fillw_inst = find_inst(VAR_FILLW, K, 64);  // (K is 2..8 here: every ploidy has one)
 #ifdef MCHAP_TEST_KERNELS
   if (T.flags & 64) {
     P.fill_lt = mchap::fill_geometry(K, P.max_pos, P.max_allele, P.d.rpad, &lds_fill);
     P.fill_kw = mchap::fill_key_words(K, P.max_pos, P.max_allele);
     lpr = P.fill_lt > 0;
   }
-#define ROW_FILL_LAUNCH(k) mchap_fill_launch_##k,
-  const simt_launch_fn fill_launches[] = {FILL_LIST(ROW_FILL_LAUNCH)};
+  const SpecInst *const fill_inst = find_inst(VAR_FILL, K, 64);
 #endif
   const int export_mode = mchap::PIPE_EXPORT | ((lpr || fillw) ? mchap::PIPE_NOFILL : 0);
   P.pipe_list = nullptr;
@@ -805,9 +755,9 @@ int launch_pipe(const Tune &T, int K, int G, mchap::SimtParams P, int n_units, i
   int e = launch(&P, grid_s, lds, stream);
   auto fill_launch = [&]() {
 #ifdef MCHAP_TEST_KERNELS
-    if (lpr) return fill_launches[K - 2](&P, (unsigned)n_chains, lds_fill, stream);
+    if (lpr) return fill_inst->launch(&P, (unsigned)n_chains, lds_fill, stream);
 #endif
-    if (fillw) return fillw_launches[K - 2](&P, (unsigned)n_chains, lds_fillw, stream);
+    if (fillw) return fillw_inst->launch(&P, (unsigned)n_chains, lds_fillw, stream);
     if (P.pipe_parts <= 1) return 0;  // (a no-op unless the chains of the list are few: pipe_parts_eff)
     mchap::SimtParams F = P;
     F.pipe_mode = mchap::PIPE_RESUME | mchap::PIPE_FILLONLY;
@@ -847,6 +797,20 @@ int launch_pipe(const Tune &T, int K, int G, mchap::SimtParams P, int n_units, i
 }
 
 }  // namespace
+
+// The kernels of two test hooks, defined here and nowhere else: this is the one translation unit that launches them.
+namespace mchap {
+// test hook (mchap_read_log_batch)
+static __global__ void read_log_kernel(const double *x, long long n, double *out) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = read_log(x[i]);
+}
+// test hook (mchap_wave_sum_batch): one wavefront per 64 values; every lane must hold the same sum
+static __global__ void wave_sum_kernel(const double *x, double *out) {
+  const double s = wave_sum(x[(size_t)blockIdx.x * WAVE + threadIdx.x]);
+  const bool same = __ballot(__double_as_longlong(s) == __double_as_longlong(__shfl(s, 0, WAVE))) == ~0ull;
+  if (threadIdx.x == 0) out[blockIdx.x] = same ? s : __longlong_as_double(0x7ff8dead00000000ll);
+}
+}  // namespace mchap
 
 extern "C" {
 
@@ -910,13 +874,10 @@ int mchap_debug_stats(unsigned long long *out, int reset) {
   HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(mchap::g_stats), sizeof(z)));
   if (reset) HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(mchap::g_stats), z, sizeof(z)));
   // plus the copies of the speculative sampler's object files
-#define ROW_SPEC_STATS(k, g) mchap_spec_stats_##k##_##g,
-#define ROW_SPECP_STATS(k, g) mchap_specp_stats_##k##_##g,
-#define ROW_SPECS_STATS(k, g) mchap_specs_stats_##k##_##g, mchap_specd_stats_##k##_##g,
-  int (*fs[])(unsigned long long *, int) = {SPEC_LIST(ROW_SPEC_STATS) SPECP_LIST(ROW_SPECP_STATS) SPECS_LIST(ROW_SPECS_STATS)};
-  for (auto f : fs) {
+  for (const SpecInst *o : SPEC_INSTS) {
+    if (o->variant > VAR_DEEP) continue;
     unsigned long long t[mchap::N_STATS];
-    if (f(t, reset) != 0) return fail(MCHAP_ERR_HIP, "reading the counters of a sampler object");
+    if (o->stats(t, reset) != 0) return fail(MCHAP_ERR_HIP, "reading the counters of a sampler object");
     for (int i = 0; i < mchap::N_STATS; i++) out[i] += t[i];
   }
   return MCHAP_OK;
@@ -925,16 +886,13 @@ int mchap_debug_stats(unsigned long long *out, int reset) {
  * [0] listing, [1] de-duplication, [2] staging, [3] evaluation, [4] probabilities + totals; [6] chunks, [7] distinct requests,
  * [8] option slots, [9] stagings, [10] batch x tile evaluations, [11] chains */
 #ifdef MCHAP_TEST_KERNELS
-#define DECL_FILL_STATS(k) extern "C" int mchap_fill_stats_##k(unsigned long long *, int);
-FILL_LIST(DECL_FILL_STATS)
 extern "C" int mchap_debug_fill_stats(unsigned long long *out, int reset) {
   HIP_TRY(hipDeviceSynchronize());
   for (int i = 0; i < mchap::N_STATS; i++) out[i] = 0;
-#define ROW_FILL_STATS(k) mchap_fill_stats_##k,
-  int (*fs[])(unsigned long long *, int) = {FILL_LIST(ROW_FILL_STATS)};
-  for (auto f : fs) {
+  for (const SpecInst *o : SPEC_INSTS) {
+    if (o->variant != VAR_FILL) continue;
     unsigned long long t[mchap::N_STATS];
-    if (f(t, reset) != 0) return fail(MCHAP_ERR_HIP, "reading the counters of a table-completion object");
+    if (o->stats(t, reset) != 0) return fail(MCHAP_ERR_HIP, "reading the counters of a table-completion object");
     for (int i = 0; i < mchap::N_STATS; i++) out[i] += t[i];
   }
   return MCHAP_OK;
@@ -942,7 +900,7 @@ extern "C" int mchap_debug_fill_stats(unsigned long long *out, int reset) {
 /* counters of the steady-state sampler's K = 4 object (its own layout: denovo_lane_kernel.hpp LPH / LCNT) */
 int mchap_debug_lane_stats(unsigned long long *out, int reset) {
   HIP_TRY(hipDeviceSynchronize());
-  if (mchap_lane_stats_4(out, reset) != 0) return fail(MCHAP_ERR_HIP, "reading the counters of the lane sampler");
+  if (LANE_INSTS[4 - 1]->stats(out, reset) != 0) return fail(MCHAP_ERR_HIP, "reading the counters of the lane sampler");
   return MCHAP_OK;
 }
 #endif
@@ -1357,7 +1315,7 @@ int mchap_read_log_product_batch(const double *x, int64_t n, int group, double *
   return hc.sync();
 }
 
-/* Test hook: wave_sum (csrc/denovo_kernel.hpp), the 64-lane sum every likelihood goes through, for n_waves x 64 values: out[w] =
+/* Test hook: wave_sum (csrc/wave_math.hpp), the 64-lane sum every likelihood goes through, for n_waves x 64 values: out[w] =
  * the sum of x[64 w .. 64 w + 63] as lane 0 holds it.  Host pointers. */
 int mchap_wave_sum_batch(const double *x, int64_t n_waves, double *out) {
   int rc = ensure_init();

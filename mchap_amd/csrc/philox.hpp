@@ -11,7 +11,6 @@
 // other program can reproduce; the order in which draws are consumed is the reference's
 // (SURVEY.md Appendix A.8).
 #pragma once
-#include "read_log.hpp"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -11,7 +11,8 @@
 #pragma once
 #include <limits.h>
 
-#include "denovo_kernel.hpp"
+#include "read_log.hpp"
+#include "wave_math.hpp"
 
 namespace mchap {
 

@@ -106,9 +106,4 @@ __device__ __forceinline__ double read_log_sum_chunks(const double (&x)[N], cons
   }
 }
 
-// test hook (mchap_read_log_batch)
-static __global__ void read_log_kernel(const double *x, long long n, double *out) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = read_log(x[i]);
-}
-
 }  // namespace mchap

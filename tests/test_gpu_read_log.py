@@ -65,7 +65,7 @@ def test_read_log_special_values():
 
 
 def test_wave_sum_tree():
-    """wave_sum (csrc/denovo_kernel.hpp): the sum over the 64 lanes of a wavefront is the XOR butterfly's tree -- offsets 32, 16,
+    """wave_sum (csrc/wave_math.hpp): the sum over the 64 lanes of a wavefront is the XOR butterfly's tree -- offsets 32, 16,
     8, 4, 2, 1 -- whatever instructions carry it (round 4: DPP row rotations for the last four steps).  Emulated here in float64
     with numpy, operand for operand; the device value must have the same bits, in every lane."""
     from mchap_amd import _lib
