@@ -369,6 +369,26 @@ int mchap_exact_em_update_device(int n_records, int n_samples, const int32_t *re
                                  double ploidy_total, double tolerance, int max_iterations, double *frequencies,
                                  int32_t *record_iterations, int32_t *record_active, double *record_delta, void *stream);
 
+/* Model evidence (call-exact --model-evidence): for every unit u and grid point n
+ *   evidence[u][n] = log sum_g P(g | ploidy, F_un, f_u) * P(reads_u | g),
+ * the normaliser of the unit's posterior under the calling prior with inbreeding F_un = inbreeding[u][n] and the frequencies of
+ * row unit_row[u] of `frequencies` [rows][stride]: the multinomial for F = 0, the Dirichlet-multinomial with alpha = f (1 - F) / F
+ * for F > 0, -inf for every genotype holding an allele of frequency 0.  These priors sum to 1 over the genotypes, so the values
+ * compare across grid points and across ploidies.  inbreeding = NULL: the flat genotype prior, n_grid = 1, unit_row and
+ * frequencies not read, evidence = logsumexp(llk) - log(G).  A unit without a finite genotype gives -inf.
+ * llks64 [U][G]: the likelihoods mchap_exact_call_batch_device leaves (llks64).  Every F must lie in [0, 1): the array is on the
+ * device, so that is the caller's duty (device.ExactModelEvidence checks its host copy), as for the estimate's inbreeding.
+ * The prior tables of as many grid points as keep a workgroup within 64 KB of LDS are built together
+ * (mchap_exact_evidence_chunk: that number, 0 where a single table exceeds 160 KB); the grid is worked in such chunks.
+ * Sums in fixed order, no atomics: equal inputs give equal bits.  `workspace`: mchap_exact_evidence_workspace_bytes (-1: more than
+ * 2^62 genotypes).  A ploidy above MCHAP_MAX_PLOIDY_DENOVO (the Python layer's MAX_PLOIDY_GENERAL) is MCHAP_ERR_LIMIT.  n_grid has
+ * no upper bound: a chunk may hold more grid points than a workgroup has threads.  Enqueues on `stream`, no synchronisation. */
+int64_t mchap_exact_evidence_workspace_bytes(int n_units, int n_haps, int ploidy, int n_grid);
+int mchap_exact_evidence_chunk(int n_haps, int ploidy, int n_grid);
+int mchap_exact_evidence_device(int n_units, const double *llks64, int n_haps, int ploidy, int n_grid, const double *inbreeding,
+                                const int32_t *unit_row, const double *frequencies, int stride, double *evidence, void *workspace,
+                                int64_t workspace_bytes, void *stream);
+
 /* Summaries of given posterior arrays [U][G] (calling.exact.posterior_allele_frequencies 332-369, the sum of
  * alternate_dosage_posteriors 372-407 for the array's mode): device pointers, any output may be NULL. */
 int mchap_exact_posterior_summaries_batch_device(int n_units, const double *posteriors, int64_t n_genotypes, int ploidy,

@@ -493,6 +493,281 @@ def estimate_prior_frequencies(units, samples, ploidy_of, inbreeding_of, iterati
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------
+# call-exact --model-evidence: log evidence of every sample's reads under candidate (ploidy, inbreeding) pairs
+# ---------------------------------------------------------------------------------------------------------
+def _genotype_table(H, K):
+    """int64 [G, K]: the ascending genotypes of K alleles out of H in VCF order (the highest allele most significant)."""
+    from itertools import chain, combinations_with_replacement
+    from math import comb
+
+    G = comb(H + K - 1, K)
+    g = np.fromiter(chain.from_iterable(combinations_with_replacement(range(H), K)), dtype=np.int64, count=G * K).reshape(G, K)
+    return g[np.lexsort(tuple(g[:, k] for k in range(K)))]
+
+
+def _host_log_prior(g, H, K, F, f):
+    """float64 [G]: the caller's normalised log prior of the genotypes g [G, K] in the form of the kernel's tables
+    (exact_kernel.hpp calling_log_prior) with math.lgamma.  F None: the flat genotype prior -log(G); F = 0: the multinomial
+    lgamma(K + 1) - sum_h lgamma(d_h + 1) + log(prod f); F > 0: the Dirichlet-multinomial with alpha = f (1 - F) / F,
+    lgamma(K + 1) + lgamma(sum alpha) - lgamma(K + sum alpha) + sum_h (lgamma(d_h + alpha_h) - lgamma(d_h + 1) - lgamma(alpha_h))."""
+    from math import inf, lgamma, log
+
+    if F is None:
+        return np.full(len(g), -log(len(g)))
+    f = np.asarray(f, dtype=np.float64)
+    occ = np.zeros(g.shape, dtype=np.int64)   # copies of the allele before this position: the run length at a run's last copy is occ + 1
+    for k in range(1, K):
+        occ[:, k] = np.where(g[:, k] == g[:, k - 1], occ[:, k - 1] + 1, 0)
+    last = np.ones(g.shape, dtype=bool)
+    last[:, :-1] = g[:, 1:] != g[:, :-1]
+    lgf = np.array([lgamma(d + 1.0) for d in range(K + 1)])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if F > 0:
+            lg = lambda x: inf if x == 0.0 else lgamma(x)
+            alpha = f * ((1.0 - F) / F)
+            lgd = np.array([[0.0 if d == 0 else lg(d + a) - (lgf[d] + lg(a)) for d in range(K + 1)] for a in alpha])
+            sa = 0.0
+            for a in alpha:
+                sa += a
+            lp = np.zeros(len(g))
+            for k in range(K):
+                lp += np.where(last[:, k], lgd[g[:, k], occ[:, k] + 1], 0.0)
+            return ((lgf[K] + lgamma(sa)) - lgamma(K + sa)) + lp
+        den, prod = np.zeros(len(g)), np.ones(len(g))
+        for k in range(K):
+            den += np.where(last[:, k], lgf[occ[:, k] + 1], 0.0)
+            prod *= f[g[:, k]]
+        return (lgf[K] - den) + np.log(prod)
+
+
+def _logsumexp(x):
+    m = np.max(x)
+    if not np.isfinite(m):   # (-inf: no genotype is finite)
+        return float(m)
+    return float(m + np.log(np.sum(np.exp(x - m))))
+
+
+def _evidence_evaluable(H, candidates, budget=None):
+    """Whether a unit of H haplotypes can be evaluated under every candidate (ploidy, F or None): the ploidy within the library's,
+    fewer than 2^62 genotypes, the prior tables of one grid point within the evidence kernel's LDS (the flat prior has none), and
+    (budget: device bytes) one unit's likelihoods within the budget."""
+    from math import comb
+
+    from . import _lib
+
+    for K in sorted({K for K, _ in candidates}):
+        if K < 1 or K > _lib.MAX_PLOIDY_GENERAL or comb(H + K - 1, K) >= 1 << 62:
+            return False
+        if any(F is not None for Kc, F in candidates if Kc == K) and int(_lib.lib().mchap_exact_evidence_chunk(H, K, 1)) == 0:
+            return False
+        if budget is not None and _exact_unit_bytes(comb(H + K - 1, K), 8) > budget:
+            return False
+    return True
+
+
+def model_evidence_host(units, samples, candidates, backend):
+    """The definition of the model evidence, in float64 on `backend` (an object with the reference's genotype_likelihoods; the oracle
+    in the CPU tests).  candidates: {sample: [(ploidy, F or None), ...]}.  For every record that needs the kernel and every sample,
+        evidence[c] = log sum_g P(g | K_c, F_c, f) P(reads | g)
+    with f the record's locus.frequencies (F None: the flat genotype prior 1 / G).  A sample without reads has evidence exactly 0
+    under every candidate (every prior sums to 1).  Returns {(record index, sample): float64 [candidates] -- or None where one of
+    the sample's candidates cannot be evaluated (_evidence_evaluable): the unit is skipped for all}."""
+    out = {}
+    for ri, unit in enumerate(units):
+        if not unit["needs_kernel"]:
+            continue
+        locus = unit["locus"]
+        H = len(locus.haplotypes)
+        tables = {}
+        for s in samples:
+            cands = candidates[s]
+            if not _evidence_evaluable(H, cands):
+                out[(ri, s)] = None
+                continue
+            sr = unit["reads"][s]
+            if len(sr["counts"]) == 0:
+                out[(ri, s)] = np.zeros(len(cands))
+                continue
+            llks, ev = {}, np.zeros(len(cands))
+            for c, (K, F) in enumerate(cands):
+                if K not in llks:
+                    llks[K] = np.asarray(backend.genotype_likelihoods(sr["dists"], K, locus.haplotypes, read_counts=sr["counts"]), dtype=np.float64)
+                if K not in tables:
+                    tables[K] = _genotype_table(H, K)
+                with np.errstate(invalid="ignore"):
+                    ev[c] = _logsumexp(llks[K] + _host_log_prior(tables[K], H, K, F, locus.frequencies))
+            out[(ri, s)] = ev
+    return out
+
+
+def _model_evidence_device(units, samples, candidates):
+    """model_evidence_host's result from the device: per candidate ploidy one likelihood pass over the units that take part
+    (llks64 alone, shape groups cut by the free HBM), then the evidence launch over the group's grid of F."""
+    from math import comb
+
+    from .device import ExactModelEvidence
+
+    out, live = {}, {}
+    budget = device_unit_budget(1, most=1 << 62)
+    for ri, unit in enumerate(units):
+        if not unit["needs_kernel"]:
+            continue
+        H = len(unit["locus"].haplotypes)
+        for s in samples:
+            cands = candidates[s]
+            if not _evidence_evaluable(H, cands, budget):
+                out[(ri, s)] = None
+            elif len(unit["reads"][s]["counts"]) == 0:
+                out[(ri, s)] = np.zeros(len(cands))
+            else:
+                out[(ri, s)] = live[(ri, s)] = np.full(len(cands), np.nan)
+    ev = ExactModelEvidence() if live else None
+    pending = []   # (members, columns of each member's candidates, device tensor): read back after everything is enqueued
+    for K in sorted({K for key in live for K, _ in candidates[key[1]]}):
+        # the units of this ploidy; a unit's grid: its candidates of ploidy K in candidate order
+        grid = {s: [(c, F) for c, (Kc, F) in enumerate(candidates[s]) if Kc == K] for s in samples}
+        for shape, group in _shape_groups(units, lambda s: K).items():
+            M, A, H, _ = shape
+            for flat in (True, False):
+                for n_grid in sorted({len(grid[s]) for _, s in group}):
+                    members = [(ri, s) for ri, s in group if (ri, s) in live and len(grid[s]) == n_grid and n_grid > 0
+                               and (grid[s][0][1] is None) == flat]
+                    if not members:
+                        continue
+                    todo = [members]
+                    while todo:
+                        part = todo.pop(0)
+                        for chunk, batch in _estimate_group_batches(units, part, shape, lambda s: 0.0, 8, prior=False):
+                            try:
+                                if batch is None:
+                                    raise NotImplementedError
+                                llks = batch.run_llks64()
+                                recs = sorted({ri for ri, _ in chunk})
+                                row = {ri: i for i, ri in enumerate(recs)}
+                                got = ev.add_group(llks, H, K, None if flat else [[F for _, F in grid[s]] for _, s in chunk],
+                                                   [row[ri] for ri, _ in chunk], np.stack([units[ri]["locus"].frequencies for ri in recs]))
+                            except NotImplementedError:
+                                # what _evidence_evaluable does not foresee (the likelihood pass refusing the chunk's depth of reads, a
+                                # workspace beyond the free memory): the chunk's units again one by one, and only a unit that is refused
+                                # on its own is skipped -- for all of its candidates
+                                if len(chunk) > 1:
+                                    todo.extend([key] for key in chunk)
+                                else:
+                                    out[chunk[0]] = None
+                                    live.pop(chunk[0], None)
+                                continue
+                            pending.append((chunk, [[c for c, _ in grid[s]] for _, s in chunk], got))
+                            del batch
+    for chunk, cols, got in pending:
+        host = got.cpu().numpy()
+        for i, key in enumerate(chunk):
+            if key in live:
+                live[key][cols[i]] = host[i]
+    return out
+
+
+class ModelEvidence:
+    """The accumulator of `call-exact --model-evidence`: per sample and candidate (ploidy, inbreeding) the sum over the records of
+    the log evidence of the sample's reads, log sum_g P(g | ploidy, F, f) P(reads | g) -- with f the frequencies the record is called
+    with -- over the records `call-exact` sends to the kernel.  The priors are normalised, so the sums of a sample compare across its
+    candidates: the best candidate is the one the reads support most (DELTA = 0), and the others' DELTA is their log Bayes factor
+    against it.  A (record, sample) that one of the sample's candidates cannot be evaluated for is left out of all of them and counted
+    in SKIPPED.
+
+    ploidies / inbreedings: the candidate values for every sample (None: the sample's own); the candidates of a sample are
+    ploidies x inbreedings in the order given, duplicates dropped.  Samples called with the flat genotype prior (no inbreeding
+    value) have one flat-prior candidate per ploidy and take no `inbreedings`.  frequency_source: "tag NAME", "flat" or
+    "estimated", stated in the table's first line."""
+
+    HEADER = ("SAMPLE", "PLOIDY", "INBREEDING", "RECORDS", "SKIPPED", "LOG_EVIDENCE", "DELTA", "CONFIGURED")
+
+    def __init__(self, samples, ploidies=None, inbreedings=None, frequency_source="flat", program="mchap_amd call-exact"):
+        self.samples = list(samples)
+        self.ploidies = None if ploidies is None else [int(K) for K in ploidies]
+        self.inbreedings = None if inbreedings is None else [float(F) for F in inbreedings]
+        if self.ploidies is not None and (not self.ploidies or any(K < 1 for K in self.ploidies)):
+            raise ValueError("model evidence: candidate ploidies are integers >= 1")
+        if self.inbreedings is not None and (not self.inbreedings or not all(0.0 <= F < 1.0 for F in self.inbreedings)):
+            raise ValueError("model evidence: candidate inbreeding values lie in [0, 1)")
+        self.frequency_source, self.program = frequency_source, program
+        self.candidates = None   # {sample: [(ploidy, F or None)]}, set by the first block
+        self.configured = None   # {sample: (ploidy, F or None)}
+        self.sums = self.records = self.skipped = None
+        self.records_seen = 0
+
+    def _configure(self, ploidy_of, inbreeding_of):
+        cands, conf = {}, {}
+        for s in self.samples:
+            K, F = int(ploidy_of(s)), inbreeding_of(s)
+            F = None if F is None else float(F)
+            if F is None and self.inbreedings is not None:
+                raise ValueError("model evidence: candidate inbreeding values need an inbreeding value for every sample "
+                                 "(--use-dirmul-prior): sample %s is called with the flat genotype prior" % s)
+            Ks = [K] if self.ploidies is None else self.ploidies
+            Fs = [F] if (self.inbreedings is None or F is None) else self.inbreedings
+            seen = []
+            for Kc in Ks:
+                for Fc in Fs:
+                    if (Kc, Fc) not in seen:
+                        seen.append((Kc, Fc))
+            cands[s], conf[s] = seen, (K, F)
+        if self.candidates is None:
+            self.candidates, self.configured = cands, conf
+            self.sums = {s: np.zeros(len(cands[s])) for s in self.samples}
+            self.records = {s: 0 for s in self.samples}
+            self.skipped = {s: 0 for s in self.samples}
+        elif conf != self.configured:
+            raise ValueError("model evidence: the samples' ploidy and inbreeding changed between blocks")
+
+    def add_block(self, units, ploidy_of, inbreeding_of, backend=None):
+        """The records of a block (what _exact_units returned, after the frequency estimate where there is one): every (record,
+        sample) that needs the kernel adds its evidence to the sample's sums, in record order.  backend: the definition on that
+        object (model_evidence_host); None = the device."""
+        self._configure(ploidy_of, inbreeding_of)
+        self.records_seen += len(units)
+        if backend is not None:
+            got = model_evidence_host(units, self.samples, self.candidates, backend)
+        else:
+            got = _model_evidence_device(units, self.samples, self.candidates)
+        for ri in range(len(units)):
+            for s in self.samples:
+                if (ri, s) not in got:
+                    continue
+                ev = got[(ri, s)]
+                if ev is None:
+                    self.skipped[s] += 1
+                else:
+                    self.sums[s] = self.sums[s] + ev
+                    self.records[s] += 1
+        return got
+
+    def table(self):
+        """The rows, in sample order then candidate order: dicts of HEADER's names in lower case (inbreeding None: flat prior)."""
+        rows = []
+        for s in self.samples if self.candidates is not None else []:
+            sums = self.sums[s]
+            best = np.max(sums) if len(sums) else 0.0
+            for c, (K, F) in enumerate(self.candidates[s]):
+                delta = 0.0 if sums[c] == best else float(sums[c] - best)
+                rows.append(dict(sample=s, ploidy=K, inbreeding=F, records=self.records[s], skipped=self.skipped[s],
+                                 log_evidence=float(sums[c]), delta=delta, configured=int((K, F) == self.configured[s])))
+        return rows
+
+    def text(self):
+        lines = ["# %s model evidence; frequencies: %s; records: %d" % (self.program, self.frequency_source, self.records_seen),
+                 "\t".join(self.HEADER)]
+        for r in self.table():
+            lines.append("\t".join([r["sample"], "%d" % r["ploidy"], "." if r["inbreeding"] is None else "%g" % r["inbreeding"],
+                                    "%d" % r["records"], "%d" % r["skipped"], "%.6f" % r["log_evidence"], "%.6f" % r["delta"],
+                                    "%d" % r["configured"]]))
+        return "\n".join(lines) + "\n"
+
+    def write(self, path):
+        with open(path, "w") as fh:
+            fh.write(self.text())
+
+
 def _per_sample(value, samples):
     """A scalar, or a {sample: value} mapping (the reference's per-sample ploidy / inbreeding files), as a function."""
     if isinstance(value, dict):
@@ -567,7 +842,7 @@ def _blocks(items, n):
 def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.0024, use_base_phred_scores=False,
                prior_frequencies_tag=None, inbreeding=None, calling=None, filter_input_haplotypes=None, read_kw=None,
                records_per_block=4096, shard=None, block_path=None, estimate_frequencies=None, estimate_tolerance=1e-6,
-               estimate_path=None):
+               estimate_path=None, model_evidence=None):
     """`mchap call-exact` over a VCF of known haplotypes: yields one VCF record line per input record (no header).
     sample_bams: ordered mapping sample name -> BAM path (or pool -> [(sample, path)], or a ReadSource); ploidy /
     inbreeding: a value or {sample: value}.  The records are processed in blocks: the (record x sample) units of a block
@@ -592,12 +867,19 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
     estimate_tolerance (estimate_prior_frequencies); the record is then called with the estimate as its prior frequencies and
     carries INFO/EMIT, the iterations run.  Every sample needs an inbreeding value.  estimate_path: None = the likelihoods stay on
     the device over the iterations where they fit and are formed again every iteration where not; "resident" / "recompute" force
-    one.  None (default): no estimate, no EMIT."""
+    one.  None (default): no estimate, no EMIT.
+
+    model_evidence: a ModelEvidence over the source's samples; every block adds to it, after the estimate and before the block's
+    records are called (the record lines do not depend on it).  Not with `shard`: the sums of several ranks are not combined."""
     from .vcfheader import report_fields
 
+    if model_evidence is not None and shard is not None:
+        raise ValueError("model_evidence runs as a single process: it does not combine the sums of several ranks (shard)")
     source = _source(sample_bams, base_error_rate, use_base_phred_scores, read_kw)
     block_path = _call_block_path(block_path, source)
     samples = source.samples
+    if model_evidence is not None and list(model_evidence.samples) != list(samples):
+        raise ValueError("model_evidence: its samples are not the source's")
     _, records = read_vcf(vcf_path)
     records = _shard(records, shard)
     report = tuple(report)
@@ -609,6 +891,8 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
         if estimate_frequencies is not None:
             estimate_prior_frequencies(units, samples, ploidy_of, inbreeding_of, estimate_frequencies, estimate_tolerance, calling,
                                        estimate_path)
+        if model_evidence is not None:
+            model_evidence.add_block(units, ploidy_of, inbreeding_of, calling)
         results = _run_exact_groups(units, ploidy_of, inbreeding_of, full, calling)
         for ri, unit in enumerate(units):
             rec = unit["rec"]

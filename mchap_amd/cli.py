@@ -11,7 +11,9 @@ sharded over the ranks and rank 0 writes the one VCF; `--reference` may name a F
 `.fai` index is present (contig lengths for the header; unknown reference bases are written as N); `--block-path
 {auto,off,on,wide}` chooses the host path of a block of targets / records (the block_path keyword of the programs); `call-exact
 --estimate-prior-frequencies N [--estimate-tolerance EPS]` estimates every record's prior allele frequencies before it is called
-(application.estimate_prior_frequencies)."""
+(application.estimate_prior_frequencies); `call-exact --model-evidence FILE [--evidence-ploidy K ...] [--evidence-inbreeding F ...]`
+also writes a table of every sample's log evidence under candidate (ploidy, inbreeding) pairs (application.ModelEvidence) and leaves
+the VCF, header included, as it is without those flags."""
 import argparse
 import sys
 
@@ -136,6 +138,15 @@ def build_parser(program):
             p.add_argument("--estimate-tolerance", type=float, nargs=1, default=[None], metavar="EPS",
                            help="(not a reference flag) with --estimate-prior-frequencies: stop a record once no frequency moves by "
                                 "EPS or more (default 1e-6)")
+            p.add_argument("--model-evidence", type=str, nargs=1, default=[None], metavar="FILE",
+                           help="(not a reference flag) write to FILE, when the run ends, a table of the log evidence of every sample's "
+                                "reads under candidate (ploidy, inbreeding) pairs, summed over the records that are called")
+            p.add_argument("--evidence-ploidy", type=int, nargs="+", default=None, metavar="K",
+                           help="(not a reference flag) with --model-evidence: candidate ploidies, 1 to 15, for every sample (default: "
+                                "the sample's own)")
+            p.add_argument("--evidence-inbreeding", type=float, nargs="+", default=None, metavar="F",
+                           help="(not a reference flag) with --model-evidence: candidate inbreeding values, 0 <= F < 1, for every sample "
+                                "(default: the sample's own); needs --use-dirmul-prior")
     p.add_argument("--report", type=str, nargs="*", default=[],
                    help="extra fields: AFPRIOR ACP AFP AOP AOPSUM GP GL SNVDP, optionally with an INFO/ or FORMAT/ prefix")
     p.add_argument("--cores", type=int, nargs=1, default=[1], help="host threads reading the alignment files")
@@ -176,7 +187,9 @@ def run(argv, out=None):
 
     out = out or sys.stdout
     program = argv[1]
-    args = build_parser(program).parse_args(argv[2:])
+    parser = build_parser(program)
+    args = parser.parse_args(argv[2:])
+    header_argv = [argv[1]] + _header_argv(argv[2:], [o for o in parser._option_string_actions if o.startswith("--")])
     if program == "find-snvs":
         return _run_find_snvs(argv, args, out)
     # must have some source of error in reads (application/arguments.py:1190-1195)
@@ -196,7 +209,7 @@ def run(argv, out=None):
                                     read_group_field=id_field, mapping_quality=args.mapping_quality[0],
                                     skip_duplicates=args.skip_duplicates, skip_qcfail=args.skip_qcfail,
                                     skip_supplementary=args.skip_supplementary, workers=args.cores[0])
-    seed = None
+    seed = evidence = None
     block_path = BLOCK_PATHS[args.block_path]
     if program == "assemble":
         if args.targets[0] is not None and args.region[0] is not None:
@@ -233,10 +246,12 @@ def run(argv, out=None):
             if estimate is not None and inbreeding is None:
                 raise ValueError("--estimate-prior-frequencies needs --use-dirmul-prior: the flat genotype prior has no allele "
                                  "frequencies to estimate")
+            evidence = model_evidence_settings(args, samples, inbreeding, tag, estimate, world)
             records = application.call_exact(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
                                              inbreeding=inbreeding, filter_input_haplotypes=args.filter_input_haplotypes[0], shard=shard,
                                              block_path=block_path, estimate_frequencies=estimate,
-                                             estimate_tolerance=1e-6 if args.estimate_tolerance[0] is None else args.estimate_tolerance[0])
+                                             estimate_tolerance=1e-6 if args.estimate_tolerance[0] is None else args.estimate_tolerance[0],
+                                             model_evidence=evidence)
         else:
             seed = args.mcmc_seed[0]
             records = application.call(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
@@ -253,7 +268,7 @@ def run(argv, out=None):
         if rank != 0:
             return n_mine
         lines = [ln for part in gathered for ln in part]
-    for line in vcfheader.header_lines(program, ["mchap_amd"] + list(argv[1:]), samples, contigs, report=report, random_seed=seed,
+    for line in vcfheader.header_lines(program, ["mchap_amd"] + header_argv, samples, contigs, report=report, random_seed=seed,
                                       estimate=program == "call-exact" and args.estimate_prior_frequencies[0] is not None):
         out.write(line + "\n")
     n = 0
@@ -263,7 +278,50 @@ def run(argv, out=None):
         n += 1
         if program == "assemble" and line.split("\t", 7)[6] == "LIMIT":
             run.limit_records += 1  # (a target beyond the build's shape limits: written with null genotypes, and main() says so)
+    if program == "call-exact" and evidence is not None:
+        evidence.write(args.model_evidence[0])
     return n
+
+
+EVIDENCE_FLAGS = ("--model-evidence", "--evidence-ploidy", "--evidence-inbreeding")
+
+
+def _header_argv(argv, options):
+    """The command line as the VCF header states it: without the model-evidence flags and their values -- the VCF, header included,
+    is byte for byte what the run writes without them.  options: the parser's option strings; a flag is resolved as argparse
+    resolves it (the exact name, else the one option it is a prefix of), so an abbreviated flag is taken out too."""
+    out, skipping = [], False
+    for a in argv:
+        if a.startswith("--"):
+            name = a.split("=", 1)[0]
+            full = [name] if name in options else [o for o in options if o.startswith(name)]
+            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS
+        if not skipping:
+            out.append(a)
+    return out
+
+
+def model_evidence_settings(args, samples, inbreeding, tag, estimate, world):
+    """The --model-evidence / --evidence-* flags of call-exact -> an application.ModelEvidence, or None without --model-evidence
+    (any --evidence-* flag is then an error)."""
+    from . import application
+
+    if args.model_evidence[0] is None:
+        for flag, value in (("--evidence-ploidy", args.evidence_ploidy), ("--evidence-inbreeding", args.evidence_inbreeding)):
+            if value is not None:
+                raise ValueError("%s needs --model-evidence" % flag)
+        return None
+    if world > 1:
+        raise ValueError("--model-evidence runs as a single process: it does not combine the sums of several ranks (WORLD_SIZE > 1)")
+    if args.evidence_ploidy is not None and not all(1 <= K <= 15 for K in args.evidence_ploidy):
+        raise ValueError("--evidence-ploidy: candidate ploidies lie in 1..15")
+    if args.evidence_inbreeding is not None:
+        if inbreeding is None:
+            raise ValueError("--evidence-inbreeding needs --use-dirmul-prior: the flat genotype prior has no inbreeding")
+        if not all(0.0 <= F < 1.0 for F in args.evidence_inbreeding):   # (False for NaN too)
+            raise ValueError("--evidence-inbreeding: candidate values lie in [0, 1)")
+    source = "estimated" if estimate is not None else ("flat" if (tag is None or inbreeding is None) else "tag %s" % tag)
+    return application.ModelEvidence(samples, args.evidence_ploidy, args.evidence_inbreeding, frequency_source=source)
 
 
 def find_snvs_call_settings(args, samples):

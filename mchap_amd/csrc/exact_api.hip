@@ -322,6 +322,67 @@ int mchap_exact_em_update_device(int n_records, int n_samples, const int32_t *re
   return MCHAP_OK;
 }
 
+// ---- model evidence over stored likelihoods: the tiles' launch, then the combine launch ----
+int64_t mchap_exact_evidence_workspace_bytes(int n_units, int n_haps, int ploidy, int n_grid) {
+  if (n_units <= 0 || n_haps < 1 || n_grid < 1 || ploidy < 1 || ploidy > MCHAP_MAX_PLOIDY_DENOVO) return 0;
+  if (!cwr_fits(n_haps, ploidy)) return -1;
+  return (int64_t)up256((size_t)n_units * (size_t)exact_nblk(host_cwr(n_haps, ploidy)) * (size_t)n_grid * 2 * 8);
+}
+
+int mchap_exact_evidence_chunk(int n_haps, int ploidy, int n_grid) {
+  if (n_haps < 1 || n_grid < 1 || ploidy < 1 || ploidy > MCHAP_MAX_PLOIDY_DENOVO) return 0;
+  return mchap::exact_ev_chunk(n_haps, ploidy, n_grid);
+}
+
+int mchap_exact_evidence_device(int n_units, const double *llks64, int n_haps, int ploidy, int n_grid, const double *inbreeding,
+                                const int32_t *unit_row, const double *frequencies, int stride, double *evidence, void *workspace,
+                                int64_t workspace_bytes, void *stream_) {
+  if (n_units <= 0) return MCHAP_OK;
+  if (!llks64 || !evidence) return fail(MCHAP_ERR_BAD_ARG, "model evidence: NULL buffer");
+  if (inbreeding && (!unit_row || !frequencies)) return fail(MCHAP_ERR_BAD_ARG, "model evidence: NULL buffer (a prior needs unit_row and frequencies)");
+  if (n_grid < 1) return fail(MCHAP_ERR_BAD_ARG, "model evidence: n_grid = %d, at least one grid point is needed", n_grid);
+  if (!inbreeding && n_grid != 1) return fail(MCHAP_ERR_BAD_ARG, "model evidence: the flat prior has one grid point, not %d", n_grid);
+  if (ploidy < 1 || ploidy > MCHAP_MAX_PLOIDY_DENOVO) return fail(MCHAP_ERR_LIMIT, "ploidy %d not in 1..%d", ploidy, MCHAP_MAX_PLOIDY_DENOVO);
+  if (n_haps < 1 || (inbreeding && stride < n_haps))
+    return fail(MCHAP_ERR_BAD_ARG, "model evidence: rows of %d doubles for %d haplotypes", stride, n_haps);
+  if (!cwr_fits(n_haps, ploidy)) return fail(MCHAP_ERR_LIMIT, "ploidy %d over %d haplotypes: more than 2^62 genotypes", ploidy, n_haps);
+  const long long G = host_cwr(n_haps, ploidy);
+  const int nblk = exact_nblk(G);
+  if ((long long)n_units * nblk > 0x7fffffffll) return fail(MCHAP_ERR_LIMIT, "model evidence: %d units x %d tiles exceed one launch", n_units, nblk);
+  const int64_t need = mchap_exact_evidence_workspace_bytes(n_units, n_haps, ploidy, n_grid);
+  if (!workspace || workspace_bytes < need)
+    return fail(MCHAP_ERR_BAD_ARG, "workspace of %lld bytes is too small: %lld needed (mchap_exact_evidence_workspace_bytes)",
+                (long long)workspace_bytes, (long long)need);
+  // (the flat prior builds no table: its LDS is the staging tile's)
+  const int chunk = inbreeding ? mchap::exact_ev_chunk(n_haps, ploidy, n_grid) : 1;
+  if (chunk == 0) return fail(MCHAP_ERR_LIMIT, "n_haps %d too large for the model evidence's prior tables", n_haps);
+  const size_t lds = mchap::exact_ev_lds(inbreeding ? n_haps : 0, ploidy, chunk);
+  int rc = ensure_init();
+  if (rc) return rc;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  mchap::ExactEvParams E;
+  std::memset(&E, 0, sizeof(E));
+  E.llk64 = llks64;
+  E.inbreeding = inbreeding;
+  E.unit_row = unit_row;
+  E.freqs = frequencies;
+  E.stride = stride;
+  E.H = n_haps; E.K = ploidy; E.nblk = nblk;
+  E.n_grid = n_grid;
+  E.chunk = chunk;
+  E.G = G;
+  E.part = reinterpret_cast<double *>(workspace);
+  E.evidence = evidence;
+  auto k = ploidy <= 8 ? mchap::exact_evidence_kernel<8> : mchap::exact_evidence_kernel<mchap::EXACT_KMAX>;
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k, dim3((unsigned)((long long)n_units * nblk)), dim3(mchap::EXACT_THREADS), lds, stream, E);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(mchap::exact_evidence_combine_kernel, dim3(n_units), dim3(64), 0, stream, E);
+  HIP_TRY(hipGetLastError());
+  return MCHAP_OK;
+}
+
 // ---- host-pointer forms: one device allocation, copies in, the device entry point, copies out ----
 int mchap_exact_genotype_likelihoods(const double *reads, int n_reads, int n_pos, int max_allele,
                                      const int64_t *read_counts, const int8_t *haplotypes, int n_haps, int ploidy,

@@ -1077,4 +1077,167 @@ static __global__ __launch_bounds__(64) void exact_em_update_kernel(const ExactE
   }
 }
 
+// ---- model evidence over stored likelihoods (application.ModelEvidence): evidence[u][n] = log sum_g P(g | K, F_n, f) P(reads | g),
+// the normaliser of the unit's posterior under prior (F_n, f), for a grid of F_n per unit.  Every prior calling_log_prior forms is
+// normalised, so the values compare across F and across ploidies.  As the estimate's iteration this is a stream over llk64 [U][G]
+// under a changing prior: the tile is staged once and walked once per grid point. ----
+struct ExactEvParams {
+  const double *llk64;       // [U][G] stored log likelihoods
+  const double *inbreeding;  // [U][n_grid], or null: the flat genotype prior (n_grid = 1), evidence = logsumexp(llk) - log(G)
+  const int32_t *unit_row;   // [U] the unit's row of freqs
+  const double *freqs;       // [rows][stride]
+  int stride;                // doubles per frequency row (>= H)
+  int H, K, nblk;
+  int n_grid;                // grid points of every unit
+  int chunk;                 // grid points whose prior tables are in the LDS together (exact_ev_chunk)
+  long long G;
+  double *part;              // [U][nblk][n_grid][2]: the tile's maximum of llk + log prior, and sum exp(. - maximum)
+  double *evidence;          // [U][n_grid]
+};
+// LDS: the staging tile of the estimate, the wavefronts' maxima and sums, `chunk` lefts, lgf, lfreq, `chunk` tables lgd [H][K + 1]
+inline size_t exact_ev_lds(int H, int K, int chunk) {
+  return ((size_t)EXACT_THREADS * EXACT_EM_PITCH + (size_t)chunk * H * (K + 1) + (K + 1) + H + 2 * (EXACT_THREADS / 64) + (size_t)chunk) * 8;
+}
+// Grid points per chunk: as many as keep the workgroup within 64 KB of LDS (two workgroups to a CU), at least one -- a single
+// table may take the LDS up to 160 KB --, 0 where not even one fits.
+inline int exact_ev_chunk(int H, int K, int n_grid) {
+  if (exact_ev_lds(H, K, 1) > 160 * 1024) return 0;
+  int c = 1;
+  while (c < n_grid && exact_ev_lds(H, K, c + 1) <= 64 * 1024) c++;
+  return c;
+}
+// One workgroup per (unit, tile of 4096 genotypes).  The tile is staged as exact_em_counts_kernel stages it, each thread unranks the
+// first genotype of its run once; then, chunk by chunk of the grid, the prior tables of the chunk's points are built and every point
+// walks the run with next_genotype.  Sums: a wavefront's 64 terms by wave_sum, a thread's steps in order, wavefronts in order, tiles
+// in order in exact_evidence_combine_kernel.  No atomics.
+template <int KM = 8>
+__global__ __launch_bounds__(EXACT_THREADS) void exact_evidence_kernel(const ExactEvParams P) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int unit = blockIdx.x / P.nblk, blk = blockIdx.x % P.nblk;
+  const int H = P.H, K = P.K, NG = P.n_grid, chunk = P.chunk;
+  constexpr int NW = EXACT_THREADS / 64;
+  const bool has_prior = P.inbreeding != nullptr;
+  double *tile = reinterpret_cast<double *>(smem);      // [EXACT_THREADS][EXACT_EM_PITCH]
+  double *redm = tile + EXACT_THREADS * EXACT_EM_PITCH;  // [NW] maxima
+  double *reds = redm + NW;                              // [NW] sums
+  double *left = reds + NW;                              // [chunk]
+  double *lgf = left + chunk;                            // [K + 1]
+  double *lfreq = lgf + (K + 1);                         // [H]       (the flat prior's launch ends here: no tables, H counted 0)
+  double *lgd = lfreq + H;                               // [chunk][H][K + 1]
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const double *fr = has_prior ? P.freqs + (size_t)P.unit_row[unit] * P.stride : nullptr;
+  const double *Fs = has_prior ? P.inbreeding + (size_t)unit * NG : nullptr;
+  const long long G = P.G;
+  const long long lo = (long long)blk * EXACT_GENOS_PER_BLOCK;
+  long long hi = lo + EXACT_GENOS_PER_BLOCK;
+  if (hi > G) hi = G;
+  const double *src = P.llk64 + (size_t)unit * G;
+#pragma unroll
+  for (int t = 0; t < EXACT_EM_RUN; t++) {
+    const int e = threadIdx.x + t * EXACT_THREADS;  // element of the tile: consecutive lanes, consecutive genotypes
+    if (lo + e < hi) tile[(e / EXACT_EM_RUN) * EXACT_EM_PITCH + (e % EXACT_EM_RUN)] = src[lo + e];
+  }
+  if (has_prior) {
+    for (int d = threadIdx.x; d <= K; d += EXACT_THREADS) lgf[d] = lgamma((double)d + 1.0);
+    for (int h = threadIdx.x; h < H; h += EXACT_THREADS) lfreq[h] = fr[h];
+  }
+  const long long first = lo + (long long)threadIdx.x * EXACT_EM_RUN;
+  lds_cdouble *mine = lds_table(tile) + threadIdx.x * EXACT_EM_PITCH;
+  int g[KM], g0[KM];
+#pragma unroll
+  for (int k = 0; k < KM; k++) g0[k] = 0;
+  if (has_prior && first < hi) unrank_genotype(first, K, g0);
+  double *out = P.part + ((size_t)unit * P.nblk + blk) * NG * 2;
+  for (int n0 = 0; n0 < NG; n0 += chunk) {
+    const int nc = (NG - n0 < chunk) ? NG - n0 : chunk;
+    __syncthreads();  // (the tables of the chunk before have been read; the first time: nothing yet)
+    if (has_prior) {
+      // the prior tables of exact_setup for every point of the chunk, from the unit's row
+      for (int q = threadIdx.x; q < nc * H * (K + 1); q += EXACT_THREADS) {
+        const int c = q / (H * (K + 1)), r = q % (H * (K + 1));
+        const int h = r / (K + 1), d = r % (K + 1);
+        const double F = Fs[n0 + c];
+        const double alpha = fr[h] * ((1.0 - F) / F);
+        lgd[q] = (F == 0.0 || d == 0) ? 0.0 : lgamma((double)d + alpha) - (lgamma((double)d + 1.0) + lgamma(alpha));
+      }
+      // (a chunk of a small shape can hold more points than the workgroup has threads: 546 at H = 2, K = 2)
+      for (int c = threadIdx.x; c < nc; c += EXACT_THREADS) {
+        const double F = Fs[n0 + c];
+        const double scale = (1.0 - F) / F;
+        double sum_alpha = 0.0;
+        for (int h = 0; h < H; h++) sum_alpha += fr[h] * scale;
+        left[c] = (F == 0.0) ? 0.0 : (lgamma((double)K + 1.0) + lgamma(sum_alpha)) - lgamma((double)K + sum_alpha);
+      }
+    }
+    __syncthreads();
+    for (int c = 0; c < nc; c++) {
+      PriorTab pt;
+      pt.lgd = lgd + (size_t)c * H * (K + 1);
+      pt.lgf = lgf;
+      pt.lfreq = lfreq;
+      pt.left = has_prior ? left[c] : 0.0;
+      pt.lnH = 0.0;
+      pt.F = has_prior ? Fs[n0 + c] : 0.0;
+      pt.has_freqs = 1;
+      // llk + log prior of the thread's run, and the tile's maximum
+      double lj[EXACT_EM_RUN];
+      double m = -INFINITY;
+#pragma unroll
+      for (int k = 0; k < KM; k++) g[k] = g0[k];
+#pragma unroll
+      for (int t = 0; t < EXACT_EM_RUN; t++) {
+        lj[t] = -INFINITY;
+        if (first + t < hi) {
+          lj[t] = mine[t];
+          if (has_prior) {
+            lj[t] += calling_log_prior(pt, g, K);
+            next_genotype(g, K);
+          }
+          if (lj[t] > m) m = lj[t];
+        }
+      }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o, WAVE));
+      if (lane == 0) redm[wave] = m;
+      __syncthreads();
+      m = redm[0];
+#pragma unroll
+      for (int w = 1; w < NW; w++) m = fmax(m, redm[w]);
+      double s = 0.0;
+#pragma unroll
+      for (int t = 0; t < EXACT_EM_RUN; t++) s += wave_sum(lj[t] > -INFINITY ? exp(lj[t] - m) : 0.0);
+      if (lane == 0) reds[wave] = s;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        double sum = 0.0;
+        for (int w = 0; w < NW; w++) sum += reds[w];
+        out[(size_t)(n0 + c) * 2] = m;
+        out[(size_t)(n0 + c) * 2 + 1] = sum;  // (a tile without a finite entry: m = -inf, every term 0)
+      }
+    }
+  }
+}
+// The tiles of a unit in order, one thread per grid point: evidence = maximum + log(total relative to it), -inf where no genotype
+// is finite; the flat prior takes its constant -log(G) here.
+static __global__ __launch_bounds__(64) void exact_evidence_combine_kernel(const ExactEvParams P) {
+  const int unit = blockIdx.x;
+  const int NG = P.n_grid;
+  const double *part = P.part + (size_t)unit * P.nblk * NG * 2;
+  for (int n = threadIdx.x; n < NG; n += blockDim.x) {
+    double m = -INFINITY;
+    for (int q = 0; q < P.nblk; q++) m = fmax(m, part[((size_t)q * NG + n) * 2]);
+    double ev = -INFINITY;
+    if (m > -INFINITY) {
+      double total = 0.0;
+      for (int q = 0; q < P.nblk; q++) {
+        const double mq = part[((size_t)q * NG + n) * 2];
+        if (mq > -INFINITY) total += part[((size_t)q * NG + n) * 2 + 1] * exp(mq - m);
+      }
+      ev = m + log(total);
+      if (P.inbreeding == nullptr) ev -= log((double)P.G);
+    }
+    P.evidence[(size_t)unit * NG + n] = ev;
+  }
+}
+
 }  // namespace mchap

@@ -668,6 +668,67 @@ class ExactFrequencyEstimate:
         return (self.d_freqs.cpu().numpy().reshape(self.n_records, self.stride), self.d_iters.cpu().numpy().astype(np.int64))
 
 
+class ExactModelEvidence:
+    """Model evidence of exact-caller units whose likelihoods are resident on the device (mchap_exact_evidence_device): for every
+    unit and every candidate inbreeding F of its grid, log sum_g P(g | ploidy, F, f) P(reads | g) -- the normaliser of the unit's
+    posterior under that prior.  The priors are normalised, so the values compare across F and across ploidies."""
+
+    def __init__(self, device=None):
+        self.torch = _torch()
+        self.device = _device(self.torch, device)
+        self.launches = 0   # groups enqueued
+
+    def _tensor(self, a, dtype, np_dtype):
+        if self.torch.is_tensor(a):
+            assert a.dtype == dtype and a.is_contiguous()
+            return a.to(self.device)
+        return self.torch.from_numpy(np.ascontiguousarray(a, dtype=np_dtype)).to(self.device)
+
+    def add_group(self, llks64, n_haps, ploidy, inbreeding_grid, unit_row, freqs):
+        """The units of one shape (n_haps, ploidy), enqueued on torch's current stream: llks64 a float64 torch tensor [U * G] on
+        the device; inbreeding_grid [U, n_grid] (or [n_grid] for all units), every F in [0, 1) -- checked here, on the host copy --,
+        or None: the flat genotype prior, one grid point, unit_row and freqs not used; unit_row [U]: each unit's row of freqs
+        [rows, stride >= n_haps] (an array, or a float64 tensor on the device).  Returns the float64 tensor [U, n_grid] on the
+        device."""
+        torch, dev = self.torch, self.device
+        H, K = int(n_haps), int(ploidy)
+        if K < 1 or K > _lib.MAX_PLOIDY_GENERAL or comb(H + K - 1, K) >= 1 << 62:
+            raise NotImplementedError("mchap_hip: ploidy %d over %d haplotypes is beyond this build's exact caller" % (K, H))
+        G = comb(H + K - 1, K)
+        assert llks64.dtype == torch.float64 and llks64.is_contiguous() and llks64.numel() % G == 0
+        U = llks64.numel() // G
+        d_F = d_row = d_fr = None
+        n_grid, stride = 1, 0
+        if inbreeding_grid is not None:
+            F = np.asarray(inbreeding_grid, dtype=np.float64)
+            if F.ndim == 1:
+                F = np.broadcast_to(F, (U, F.shape[0]))
+            if F.ndim != 2 or F.shape[0] != U or F.shape[1] < 1:
+                raise ValueError("inbreeding_grid: [U, n_grid] with n_grid >= 1, got %r for %d units" % (F.shape, U))
+            if not np.all((F >= 0.0) & (F < 1.0)):   # (False for NaN and infinities too)
+                raise ValueError("inbreeding_grid: every F must lie in [0, 1)")
+            n_grid = int(F.shape[1])
+            d_F = torch.from_numpy(np.ascontiguousarray(F)).to(dev)
+            d_row = self._tensor(unit_row, torch.int32, np.int32)
+            d_fr = self._tensor(freqs, torch.float64, np.float64)
+            assert d_row.numel() == U and d_fr.dim() == 2
+            stride = int(d_fr.shape[1])
+            if U and not torch.is_tensor(unit_row):
+                rows = np.asarray(unit_row)
+                assert int(rows.min()) >= 0 and int(rows.max()) < int(d_fr.shape[0])
+        out = torch.empty((U, n_grid), dtype=torch.float64, device=dev)
+        if U == 0:
+            return out
+        L = _lib.lib()
+        wsb = int(L.mchap_exact_evidence_workspace_bytes(U, H, K, n_grid))
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+        _lib.check(L.mchap_exact_evidence_device(
+            U, _ptr(llks64), H, K, n_grid, _ptr(d_F), _ptr(d_row), _ptr(d_fr), stride, _ptr(out), _ptr(ws), C.c_int64(wsb),
+            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        self.launches += 1
+        return out
+
+
 class DenovoRaggedBatch(_OwnBuffers):
     """Units of different shapes (loci with different numbers of SNVs and alleles, samples with different read depths,
     per-sample ploidy / inbreeding) in ONE sampler launch, with the posterior summary and the replicate incongruence
