@@ -389,6 +389,30 @@ int mchap_exact_evidence_device(int n_units, const double *llks64, int n_haps, i
                                 const int32_t *unit_row, const double *frequencies, int stride, double *evidence, void *workspace,
                                 int64_t workspace_bytes, void *stream);
 
+/* SNV genotype posteriors (call-exact --snv-calls): for every unit u, SNV j and SNV genotype s
+ *   snv_post[u][j][s] = sum_g p_u[g] [s_j(g) = s],   p_u[g] = exp(llk_u[g] + log prior_u[g] - log_norm[u]),
+ * the unit's haplotype-genotype posterior under the calling prior (as the model evidence: inbreeding[u] and row unit_row[u] of
+ * `frequencies`; inbreeding = NULL: the flat genotype prior, frequencies not read) added to the SNV genotype it implies.
+ * hap_alleles [rows][n_haps][n_pos]: the SNV allele 0 .. n_snv_alleles - 1 (n_snv_alleles <= 4) of every haplotype at every SNV,
+ * the row of a unit again unit_row[u]; s_j(g) is the rank in VCF order of the multiset of the SNV alleles of g's haplotypes among
+ * the S = C(n_snv_alleles + ploidy - 1, ploidy) SNV genotypes.  VCF order nests, so an SNV with fewer alleles fills a prefix of its
+ * row and the rest is exactly 0.  log_norm [U] (may be NULL): the normaliser, the unit's model evidence at its own F.  A unit
+ * without a finite genotype gives NaN everywhere (log_norm -inf).
+ * Two passes: the evidence launches for log_norm, then every p[g] is added as a 64-bit integer with 62 fraction bits (LDS integer
+ * atomics, tiles summed as integers): equal inputs give equal bits whatever the order of the units, and an entry is off by less
+ * than G * 2^-62 from the sum of the float64 terms.  The bins of as many SNVs as keep a workgroup within 64 KB of LDS are held
+ * together (mchap_exact_snv_chunk: that number, a single SNV may take up to 160 KB, 0 where not even one fits); the SNVs are
+ * worked in such chunks, so n_pos has no upper bound.  `workspace`: mchap_exact_snv_workspace_bytes (-1: a ploidy outside
+ * 1..MCHAP_MAX_PLOIDY_DENOVO or more than 2^62 genotypes -- the call itself is MCHAP_ERR_LIMIT).  Every F must lie in [0, 1) and
+ * every SNV allele in its range: the arrays are on the device, so that is the caller's duty (device.ExactSnvPosteriors checks its
+ * host copies).  Enqueues on `stream`, no synchronisation. */
+int64_t mchap_exact_snv_workspace_bytes(int n_units, int n_haps, int ploidy, int n_pos, int n_snv_alleles);
+int mchap_exact_snv_chunk(int n_haps, int ploidy, int n_pos, int n_snv_alleles);
+int mchap_exact_snv_posteriors_device(int n_units, const double *llks64, int n_haps, int ploidy, int n_pos, int n_snv_alleles,
+                                      const double *inbreeding, const int32_t *unit_row, const double *frequencies, int stride,
+                                      const int8_t *hap_alleles, double *snv_post, double *log_norm, void *workspace,
+                                      int64_t workspace_bytes, void *stream);
+
 /* Summaries of given posterior arrays [U][G] (calling.exact.posterior_allele_frequencies 332-369, the sum of
  * alternate_dosage_posteriors 372-407 for the array's mode): device pointers, any output may be NULL. */
 int mchap_exact_posterior_summaries_batch_device(int n_units, const double *posteriors, int64_t n_genotypes, int ploidy,

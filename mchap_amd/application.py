@@ -768,6 +768,215 @@ class ModelEvidence:
             fh.write(self.text())
 
 
+# ---------------------------------------------------------------------------------------------------------
+# call-exact --snv-calls: the SNV-level VCF of a run, with GQ / DS / ACP / GP from the exact SNV genotype posteriors
+# ---------------------------------------------------------------------------------------------------------
+SNV_MAX_ALLELES = 4   # SNV alleles a haplotype table may hold (the bases): what the kernel's rank takes
+
+
+def _snv_genotype_ranks(g, alleles):
+    """int64 [G]: for every genotype of g [G, K] the rank in VCF order of the SNV genotype it implies -- the multiset of
+    alleles[g_k], `alleles` int [H] the SNV allele of every haplotype."""
+    from math import comb
+
+    K = g.shape[1]
+    a = np.sort(np.asarray(alleles, dtype=np.int64)[g], axis=1)
+    cw = np.array([[comb(n + i, i + 1) for i in range(K)] for n in range(int(a.max()) + 1)], dtype=np.int64)
+    rank = np.zeros(len(g), dtype=np.int64)
+    for i in range(K):
+        rank += cw[a[:, i], i]
+    return rank
+
+
+def snv_posterior_unit(llk, H, K, F, f, hap_alleles, n_snv_alleles=None):
+    """The definition for one unit, in float64: snv_post float64 [M, S] with
+        snv_post[j][s] = sum_g p[g] [s_j(g) = s],   p[g] = exp(llk[g] + lp[g] - logsumexp(llk + lp)),
+    lp the normalised calling prior (_host_log_prior; F None: flat), hap_alleles int [H, M] the SNV allele of every haplotype at
+    every SNV (first appearance over the haplotypes), s_j(g) the rank in VCF order of the multiset of the SNV alleles of g's
+    haplotypes at SNV j, S = C(A + K - 1, K) for A = n_snv_alleles (None: the largest number of alleles of an SNV).  VCF order
+    nests: an SNV with fewer alleles fills a prefix of its row, the rest is exactly 0.  NaN everywhere where no genotype has a
+    finite llk + lp."""
+    from math import comb
+
+    ha = np.asarray(hap_alleles, dtype=np.int64).reshape(H, -1)
+    M = ha.shape[1]
+    A = int(ha.max()) + 1 if n_snv_alleles is None and ha.size else int(n_snv_alleles or 1)
+    S = comb(A + K - 1, K)
+    g = _genotype_table(H, K)
+    with np.errstate(invalid="ignore", over="ignore"):
+        lj = np.asarray(llk, dtype=np.float64) + _host_log_prior(g, H, K, F, f)
+        norm = _logsumexp(lj)
+        if not np.isfinite(norm):
+            return np.full((M, S), np.nan)
+        p = np.where(lj > -np.inf, np.exp(lj - norm), 0.0)
+    out = np.zeros((M, S))
+    for j in range(M):
+        out[j] = np.bincount(_snv_genotype_ranks(g, ha[:, j]), weights=p, minlength=S)
+    return out
+
+
+def _snv_evaluable(unit, K):
+    """Whether the SNV posteriors of a unit that needs the kernel are formed: a ploidy and a genotype count within the library's,
+    and at most SNV_MAX_ALLELES alleles at every SNV."""
+    from math import comb
+
+    from ._lib import MAX_PLOIDY_GENERAL
+
+    haps = unit["locus"].haplotypes
+    return 1 <= K <= MAX_PLOIDY_GENERAL and comb(len(haps) + K - 1, K) < 1 << 62 and (haps.size == 0 or int(haps.max()) < SNV_MAX_ALLELES)
+
+
+def snv_posteriors_host(units, samples, ploidy_of, inbreeding_of, backend):
+    """The definition of the SNV genotype posteriors, in float64 on `backend` (an object with the reference's genotype_likelihoods;
+    the oracle in the CPU tests): for every record that needs the kernel and every sample, snv_posterior_unit of the sample's
+    likelihoods under its calling prior (inbreeding_of(sample), the record's locus.frequencies; None: flat) with the record's
+    locus.haplotypes as the SNV alleles.  A sample without reads has an all-zero likelihood table: its posterior is its prior.
+    Returns {(record index, sample): float64 [M, S] -- or None where it is not formed (_snv_evaluable)}."""
+    from math import comb
+
+    out = {}
+    for ri, unit in enumerate(units):
+        if not unit["needs_kernel"]:
+            continue
+        locus = unit["locus"]
+        H = len(locus.haplotypes)
+        for s in samples:
+            K = int(ploidy_of(s))
+            if not _snv_evaluable(unit, K):
+                out[(ri, s)] = None
+                continue
+            sr = unit["reads"][s]
+            if len(sr["counts"]) == 0:
+                llk = np.zeros(comb(H + K - 1, K))
+            else:
+                llk = np.asarray(backend.genotype_likelihoods(sr["dists"], K, locus.haplotypes, read_counts=sr["counts"]), dtype=np.float64)
+            out[(ri, s)] = snv_posterior_unit(llk, H, K, inbreeding_of(s), locus.frequencies, locus.haplotypes)
+    return out
+
+
+def _snv_posteriors_device(units, samples, ploidy_of, inbreeding_of):
+    """snv_posteriors_host's result from the device: per shape group one likelihood pass (llks64 alone, cut by the free HBM), then
+    the SNV launch over the group; the results are read back after everything is enqueued.  A chunk the library refuses is run
+    again unit by unit, and a unit refused on its own has no SNV posterior (None)."""
+    from math import comb
+
+    from .device import ExactSnvPosteriors
+
+    out, pending = {}, []
+    snv = None
+    for shape, group in _shape_groups(units, ploidy_of).items():
+        M, A, H, K = shape
+        for ri, s in group:
+            if not _snv_evaluable(units[ri], K):
+                out[(ri, s)] = None
+        for flat in (True, False):
+            members = [key for key in group if key not in out and (inbreeding_of(key[1]) is None) == flat]
+            todo = [members] if members else []
+            while todo:
+                part = todo.pop(0)
+                for chunk, batch in _estimate_group_batches(units, part, shape, lambda s: 0.0, 8, prior=False):
+                    try:
+                        if batch is None:
+                            raise NotImplementedError
+                        llks = batch.run_llks64()
+                        recs = sorted({ri for ri, _ in chunk})
+                        row = {ri: i for i, ri in enumerate(recs)}
+                        if snv is None:
+                            snv = ExactSnvPosteriors()
+                        got = snv.add_group(llks, H, K, None if flat else [inbreeding_of(s) for _, s in chunk], [row[ri] for ri, _ in chunk],
+                                            np.stack([units[ri]["locus"].frequencies for ri in recs]),
+                                            np.stack([units[ri]["locus"].haplotypes for ri in recs]))
+                    except NotImplementedError:
+                        if len(chunk) > 1:
+                            todo.extend([key] for key in chunk)
+                        else:
+                            out[chunk[0]] = None
+                        continue
+                    pending.append((chunk, K, got))
+                    del batch
+    for chunk, K, got in pending:
+        host = got.cpu().numpy()
+        for i, (ri, s) in enumerate(chunk):
+            S = comb(int(units[ri]["locus"].haplotypes.max()) + K, K)   # (the record's own alleles: a prefix of the group's rows)
+            out[(ri, s)] = host[i][:, :S].copy()
+    return out
+
+
+class SnvCalls:
+    """The writer of `call-exact --snv-calls`: the SNV-level VCF `atomize` would make of the run's own record lines (one record per
+    basis SNV, GT:GQ:PQ:DP:DS), written during the run, with the fields the exact caller can do better taken from the SNV genotype
+    posteriors: GQ is the posterior probability of the projected call's SNV genotype as a quality ('.' where the sample has no
+    call or no SNV posterior), DS the expected ALT dosages and INFO/ACP their sum over the samples with the REF entry -- present
+    whatever --report asked for --, and with report=("GP",) a sixth field GP, the SNV genotype posteriors in VCF order.
+
+    samples: the source's; contig_lines: the ##contig lines of the header; command: the header's command line."""
+
+    def __init__(self, samples, contig_lines=(), report=(), command="mchap_amd call-exact"):
+        self.samples = list(samples)
+        report = tuple(report or ())
+        if any(r != "GP" for r in report):
+            raise ValueError("snv report: GP is the one optional field, got %s" % ", ".join(report))
+        self.gp = "GP" in report
+        self.contig_lines, self.command = list(contig_lines), command
+        self.lines = []
+
+    def add_block(self, units, lines, ploidy_of, inbreeding_of, backend=None):
+        """The records of a block (what _exact_units returned) and their record lines as the main VCF shows them: the block's SNV
+        record lines are added.  backend: the definition on that object (snv_posteriors_host); None = the device.  Returns the
+        posteriors {(record index, sample): float64 [M, S] or None}."""
+        from math import comb
+
+        from . import atomize
+        from .io import qual_of_prob, vcf_record
+
+        if backend is not None:
+            post = snv_posteriors_host(units, self.samples, ploidy_of, inbreeding_of, backend)
+        else:
+            post = _snv_posteriors_device(units, self.samples, ploidy_of, inbreeding_of)
+        for ri, (unit, line) in enumerate(zip(units, lines)):
+            rec = vcf_record(line.split("\t"), self.samples)
+            snvs = atomize.haplotype_snvs(rec)
+            if snvs is None:
+                continue
+            idx = atomize.snv_allele_indices(snvs)
+            H, M = idx.shape
+            gts = atomize.record_genotypes(rec, self.samples)
+            counts = np.full((M, len(self.samples), atomize.MAX_SNV_ALLELES), np.nan)
+            gq = [["."] * len(self.samples) for _ in range(M)]
+            gp = [["."] * len(self.samples) for _ in range(M)] if self.gp else None
+            for i, s in enumerate(self.samples):
+                K = len(gts[s])
+                p = post.get((ri, s))
+                if p is None and H == 1 and unit["invalid"] is None:
+                    p = np.ones((M, 1))   # (a single haplotype needs no kernel: its one genotype has probability 1)
+                if p is None:
+                    continue
+                dosage = np.zeros((p.shape[1], atomize.MAX_SNV_ALLELES))   # copies of every SNV allele in every SNV genotype
+                for k in range(K):
+                    np.add.at(dosage, (np.arange(p.shape[1]), _genotype_table(atomize.MAX_SNV_ALLELES, K)[:p.shape[1], k]), 1.0)
+                counts[:, i, :] = p @ dosage
+                called = all(a is not None for a in gts[s])
+                for j in range(M):
+                    if called and not np.isnan(p[j, 0]):
+                        gq[j][i] = str(qual_of_prob(float(p[j, atomize.genotype_rank(idx[a, j] for a in gts[s])])))
+                    if gp is not None:
+                        gp[j][i] = ",".join(atomize.float_text(v) for v in p[j, :comb(int(idx[:, j].max()) + K, K)])
+            self.lines.extend(atomize.snv_block_lines(rec, self.samples, dict(gq=gq, counts=counts, gp=gp)))
+        return post
+
+    def header(self):
+        from . import atomize
+
+        return atomize.snv_header_lines(self.contig_lines, self.samples, self.command, gp=self.gp)
+
+    def text(self):
+        return "\n".join(self.header() + self.lines) + "\n"
+
+    def write(self, path):
+        with open(path, "w") as fh:
+            fh.write(self.text())
+
+
 def _per_sample(value, samples):
     """A scalar, or a {sample: value} mapping (the reference's per-sample ploidy / inbreeding files), as a function."""
     if isinstance(value, dict):
@@ -842,7 +1051,7 @@ def _blocks(items, n):
 def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.0024, use_base_phred_scores=False,
                prior_frequencies_tag=None, inbreeding=None, calling=None, filter_input_haplotypes=None, read_kw=None,
                records_per_block=4096, shard=None, block_path=None, estimate_frequencies=None, estimate_tolerance=1e-6,
-               estimate_path=None, model_evidence=None):
+               estimate_path=None, model_evidence=None, snv_calls=None):
     """`mchap call-exact` over a VCF of known haplotypes: yields one VCF record line per input record (no header).
     sample_bams: ordered mapping sample name -> BAM path (or pool -> [(sample, path)], or a ReadSource); ploidy /
     inbreeding: a value or {sample: value}.  The records are processed in blocks: the (record x sample) units of a block
@@ -870,16 +1079,24 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
     one.  None (default): no estimate, no EMIT.
 
     model_evidence: a ModelEvidence over the source's samples; every block adds to it, after the estimate and before the block's
-    records are called (the record lines do not depend on it).  Not with `shard`: the sums of several ranks are not combined."""
+    records are called (the record lines do not depend on it).  Not with `shard`: the sums of several ranks are not combined.
+
+    snv_calls: a SnvCalls over the source's samples; every block's SNV record lines are added to it after the block's records are
+    called, from the very lines yielded here and the exact SNV genotype posteriors (the record lines do not depend on it).  Not
+    with `shard`: the SNV file is written by one process."""
     from .vcfheader import report_fields
 
     if model_evidence is not None and shard is not None:
         raise ValueError("model_evidence runs as a single process: it does not combine the sums of several ranks (shard)")
+    if snv_calls is not None and shard is not None:
+        raise ValueError("snv_calls runs as a single process: the SNV file is not gathered from several ranks (shard)")
     source = _source(sample_bams, base_error_rate, use_base_phred_scores, read_kw)
     block_path = _call_block_path(block_path, source)
     samples = source.samples
     if model_evidence is not None and list(model_evidence.samples) != list(samples):
         raise ValueError("model_evidence: its samples are not the source's")
+    if snv_calls is not None and list(snv_calls.samples) != list(samples):
+        raise ValueError("snv_calls: its samples are not the source's")
     _, records = read_vcf(vcf_path)
     records = _shard(records, shard)
     report = tuple(report)
@@ -894,12 +1111,20 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
         if model_evidence is not None:
             model_evidence.add_block(units, ploidy_of, inbreeding_of, calling)
         results = _run_exact_groups(units, ploidy_of, inbreeding_of, full, calling)
+        lines = []
         for ri, unit in enumerate(units):
             rec = unit["rec"]
             flt, info, fmt, cols = _format_exact_record(unit, samples, results, ri, ploidy_of, report, prior_frequencies_tag)
             alts = unit["locus"].sequences[1:]  # (the input's, minus the alleles --filter-input-haplotypes removed)
             alt = ",".join(alts) if alts else "."
-            yield "\t".join([rec["chrom"], str(rec["pos"]), rec["id"], rec["ref"], alt, ".", flt, info, fmt] + [cols[s] for s in samples])
+            line = "\t".join([rec["chrom"], str(rec["pos"]), rec["id"], rec["ref"], alt, ".", flt, info, fmt] + [cols[s] for s in samples])
+            if snv_calls is None:
+                yield line
+            else:
+                lines.append(line)
+        if snv_calls is not None:
+            snv_calls.add_block(units, lines, ploidy_of, inbreeding_of, calling)
+            yield from lines
 
 
 def _shard(items, shard):

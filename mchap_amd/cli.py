@@ -1,4 +1,4 @@
-"""Command line of the programs built on the kernels: `python -m mchap_amd {assemble,call,call-exact,find-snvs} ...` with the
+"""Command line of the programs built on the kernels: `python -m mchap_amd {assemble,call,call-exact,find-snvs,atomize} ...` with the
 reference's flag names, defaults and meaning (application/cli.py:14-60; application/arguments.py: the argument tables
 ASSEMBLE_MCMC_PARSER_ARGUMENTS / CALL_EXACT_PARSER_ARGUMENTS / CALL_MCMC_PARSER_ARGUMENTS and the collect_* functions)
 for these three programs: every flag those tables define is accepted here with the same arity and default.  Output: a VCF
@@ -13,13 +13,15 @@ sharded over the ranks and rank 0 writes the one VCF; `--reference` may name a F
 --estimate-prior-frequencies N [--estimate-tolerance EPS]` estimates every record's prior allele frequencies before it is called
 (application.estimate_prior_frequencies); `call-exact --model-evidence FILE [--evidence-ploidy K ...] [--evidence-inbreeding F ...]`
 also writes a table of every sample's log evidence under candidate (ploidy, inbreeding) pairs (application.ModelEvidence) and leaves
-the VCF, header included, as it is without those flags."""
+the VCF, header included, as it is without those flags; so does `call-exact --snv-calls FILE [--snv-report GP]`, which writes the
+SNV-level VCF `atomize` would make of the run's output with GQ, DS and ACP from the exact SNV genotype posteriors
+(application.SnvCalls).  `atomize --haplotypes FILE` is host only (mchap_amd/atomize.py)."""
 import argparse
 import sys
 
 from . import __version__
 
-PROGRAMS = ("assemble", "call", "call-exact", "find-snvs")
+PROGRAMS = ("assemble", "call", "call-exact", "find-snvs", "atomize")
 
 
 def _flag(p, name, dest, action, help):
@@ -70,6 +72,13 @@ def _mcmc_args(p):
 def build_parser(program):
     """The parser of one program: the flags of the reference's argument table for it (application/arguments.py:742-838)."""
     p = argparse.ArgumentParser("mchap_amd " + program)
+    if program == "atomize":
+        # (reference application/atomize.py main: its one flag)
+        p.add_argument("--haplotypes", type=str, nargs=1, default=[None],
+                       help="VCF (text or bgzip) of haplotype calls to split into basis SNVs; it must carry INFO/SNVPOS.  INFO/DP and "
+                            "FORMAT/DP come from FORMAT/SNVDP, INFO/ACP and FORMAT/DS from FORMAT/ACP or FORMAT/AFP where present "
+                            "(normalised where they do not sum to the ploidy or to one)")
+        return p
     if program == "find-snvs":
         # (reference application/find_snvs.py main: its argument list; --cores as the other programs have it)
         p.add_argument("--targets", type=str, nargs=1, default=[None], help="BED file (3+ columns) of the intervals to search")
@@ -147,6 +156,12 @@ def build_parser(program):
             p.add_argument("--evidence-inbreeding", type=float, nargs="+", default=None, metavar="F",
                            help="(not a reference flag) with --model-evidence: candidate inbreeding values, 0 <= F < 1, for every sample "
                                 "(default: the sample's own); needs --use-dirmul-prior")
+            p.add_argument("--snv-calls", type=str, nargs=1, default=[None], metavar="FILE",
+                           help="(not a reference flag) write to FILE, when the run ends, the SNV-level VCF `atomize` would make of this "
+                                "run's output (one record per basis SNV, GT:GQ:PQ:DP:DS), with GQ, DS and INFO/ACP from the exact SNV "
+                                "genotype posteriors")
+            p.add_argument("--snv-report", type=str, nargs="+", default=None, metavar="FIELD", choices=["GP"],
+                           help="(not a reference flag) with --snv-calls: GP adds the SNV genotype posteriors as a sixth FORMAT field")
     p.add_argument("--report", type=str, nargs="*", default=[],
                    help="extra fields: AFPRIOR ACP AFP AOP AOPSUM GP GL SNVDP, optionally with an INFO/ or FORMAT/ prefix")
     p.add_argument("--cores", type=int, nargs=1, default=[1], help="host threads reading the alignment files")
@@ -192,6 +207,8 @@ def run(argv, out=None):
     header_argv = [argv[1]] + _header_argv(argv[2:], [o for o in parser._option_string_actions if o.startswith("--")])
     if program == "find-snvs":
         return _run_find_snvs(argv, args, out)
+    if program == "atomize":
+        return _run_atomize(argv, args, out)
     # must have some source of error in reads (application/arguments.py:1190-1195)
     if args.ignore_base_phred_scores and args.base_error_rate[0] == 0.0:
         raise ValueError("Cannot ignore base phred scores if --base-error-rate is 0")
@@ -209,7 +226,7 @@ def run(argv, out=None):
                                     read_group_field=id_field, mapping_quality=args.mapping_quality[0],
                                     skip_duplicates=args.skip_duplicates, skip_qcfail=args.skip_qcfail,
                                     skip_supplementary=args.skip_supplementary, workers=args.cores[0])
-    seed = evidence = None
+    seed = evidence = snv_calls = None
     block_path = BLOCK_PATHS[args.block_path]
     if program == "assemble":
         if args.targets[0] is not None and args.region[0] is not None:
@@ -247,11 +264,12 @@ def run(argv, out=None):
                 raise ValueError("--estimate-prior-frequencies needs --use-dirmul-prior: the flat genotype prior has no allele "
                                  "frequencies to estimate")
             evidence = model_evidence_settings(args, samples, inbreeding, tag, estimate, world)
+            snv_calls = snv_calls_settings(args, samples, world, ["mchap_amd"] + header_argv)
             records = application.call_exact(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
                                              inbreeding=inbreeding, filter_input_haplotypes=args.filter_input_haplotypes[0], shard=shard,
                                              block_path=block_path, estimate_frequencies=estimate,
                                              estimate_tolerance=1e-6 if args.estimate_tolerance[0] is None else args.estimate_tolerance[0],
-                                             model_evidence=evidence)
+                                             model_evidence=evidence, snv_calls=snv_calls)
         else:
             seed = args.mcmc_seed[0]
             records = application.call(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
@@ -280,14 +298,18 @@ def run(argv, out=None):
             run.limit_records += 1  # (a target beyond the build's shape limits: written with null genotypes, and main() says so)
     if program == "call-exact" and evidence is not None:
         evidence.write(args.model_evidence[0])
+    if snv_calls is not None:
+        snv_calls.write(args.snv_calls[0])
     return n
 
 
 EVIDENCE_FLAGS = ("--model-evidence", "--evidence-ploidy", "--evidence-inbreeding")
+# the flags of the SNV file: left out of the header's command line as the evidence flags are
+SNV_FLAGS = ("--snv-calls", "--snv-report")
 
 
 def _header_argv(argv, options):
-    """The command line as the VCF header states it: without the model-evidence flags and their values -- the VCF, header included,
+    """The command line as the VCF header states it: without the model-evidence and SNV-file flags and their values -- the VCF, header included,
     is byte for byte what the run writes without them.  options: the parser's option strings; a flag is resolved as argparse
     resolves it (the exact name, else the one option it is a prefix of), so an abbreviated flag is taken out too."""
     out, skipping = [], False
@@ -295,7 +317,7 @@ def _header_argv(argv, options):
         if a.startswith("--"):
             name = a.split("=", 1)[0]
             full = [name] if name in options else [o for o in options if o.startswith(name)]
-            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS
+            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS + SNV_FLAGS
         if not skipping:
             out.append(a)
     return out
@@ -322,6 +344,30 @@ def model_evidence_settings(args, samples, inbreeding, tag, estimate, world):
             raise ValueError("--evidence-inbreeding: candidate values lie in [0, 1)")
     source = "estimated" if estimate is not None else ("flat" if (tag is None or inbreeding is None) else "tag %s" % tag)
     return application.ModelEvidence(samples, args.evidence_ploidy, args.evidence_inbreeding, frequency_source=source)
+
+
+def snv_calls_settings(args, samples, world, command):
+    """The --snv-calls / --snv-report flags of call-exact -> an application.SnvCalls, or None without --snv-calls (--snv-report is
+    then an error)."""
+    from . import application, atomize
+
+    if args.snv_calls[0] is None:
+        if args.snv_report is not None:
+            raise ValueError("--snv-report needs --snv-calls")
+        return None
+    if world > 1:
+        raise ValueError("--snv-calls runs as a single process: the SNV file is not gathered from several ranks (WORLD_SIZE > 1)")
+    return application.SnvCalls(samples, atomize.vcf_contig_lines(args.haplotypes[0]), report=args.snv_report or (), command=command)
+
+
+def _run_atomize(argv, args, out):
+    """atomize: the SNV file of a haplotype VCF on `out`; host only."""
+    from . import atomize
+
+    if args.haplotypes[0] is None:
+        raise ValueError("--haplotypes is required")
+    sys.stderr.write("mchap_amd atomize: the reference marks this program as experimental\n")
+    return atomize.atomize_vcf(args.haplotypes[0], out, command=["mchap_amd"] + list(argv[1:]))
 
 
 def find_snvs_call_settings(args, samples):

@@ -383,6 +383,104 @@ int mchap_exact_evidence_device(int n_units, const double *llks64, int n_haps, i
   return MCHAP_OK;
 }
 
+// ---- SNV genotype posteriors over stored likelihoods: the evidence launches at the unit's own F for the normaliser, then the
+// tiles' launch and the combine launch ----
+}  // extern "C"
+
+namespace {
+// carve of the caller's workspace: the evidence pass' partials, the normalisers, the tiles' fixed-point sums
+struct SnvCarve {
+  size_t ev = 0, norm = 0, part = 0, bytes = 0;
+};
+SnvCarve snv_carve(int n_units, int n_haps, int ploidy, int n_pos, int n_snv_alleles) {
+  const size_t nb = (size_t)exact_nblk(host_cwr(n_haps, ploidy));
+  const size_t S = (size_t)host_cwr(n_snv_alleles, ploidy);
+  SnvCarve c;
+  size_t o = 0;
+  c.ev = o; o += up256((size_t)n_units * nb * 2 * 8);
+  c.norm = o; o += up256((size_t)n_units * 8);
+  c.part = o; o += up256((size_t)n_units * nb * (size_t)n_pos * S * 8);
+  c.bytes = o;
+  return c;
+}
+bool snv_shape(int n_haps, int ploidy, int n_pos, int n_snv_alleles) {
+  return n_haps >= 1 && n_pos >= 1 && n_snv_alleles >= 1 && n_snv_alleles <= mchap::SNV_MAX_ALLELES && ploidy >= 1 &&
+         ploidy <= MCHAP_MAX_PLOIDY_DENOVO;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t mchap_exact_snv_workspace_bytes(int n_units, int n_haps, int ploidy, int n_pos, int n_snv_alleles) {
+  if (ploidy < 1 || ploidy > MCHAP_MAX_PLOIDY_DENOVO || !cwr_fits(n_haps, ploidy)) return -1;  // (the call itself: MCHAP_ERR_LIMIT)
+  if (n_units <= 0 || !snv_shape(n_haps, ploidy, n_pos, n_snv_alleles)) return 0;
+  return (int64_t)snv_carve(n_units, n_haps, ploidy, n_pos, n_snv_alleles).bytes;
+}
+
+int mchap_exact_snv_chunk(int n_haps, int ploidy, int n_pos, int n_snv_alleles) {
+  if (!snv_shape(n_haps, ploidy, n_pos, n_snv_alleles)) return 0;
+  return mchap::exact_snv_chunk(n_haps, ploidy, (int)host_cwr(n_snv_alleles, ploidy), n_pos);
+}
+
+int mchap_exact_snv_posteriors_device(int n_units, const double *llks64, int n_haps, int ploidy, int n_pos, int n_snv_alleles,
+                                      const double *inbreeding, const int32_t *unit_row, const double *frequencies, int stride,
+                                      const int8_t *hap_alleles, double *snv_post, double *log_norm, void *workspace,
+                                      int64_t workspace_bytes, void *stream_) {
+  if (n_units <= 0) return MCHAP_OK;
+  if (!llks64 || !unit_row || !hap_alleles || !snv_post) return fail(MCHAP_ERR_BAD_ARG, "SNV posteriors: NULL buffer");
+  if (inbreeding && !frequencies) return fail(MCHAP_ERR_BAD_ARG, "SNV posteriors: NULL buffer (a prior needs frequencies)");
+  if (ploidy < 1 || ploidy > MCHAP_MAX_PLOIDY_DENOVO) return fail(MCHAP_ERR_LIMIT, "ploidy %d not in 1..%d", ploidy, MCHAP_MAX_PLOIDY_DENOVO);
+  if (n_haps < 1 || (inbreeding && stride < n_haps))
+    return fail(MCHAP_ERR_BAD_ARG, "SNV posteriors: rows of %d doubles for %d haplotypes", stride, n_haps);
+  if (n_snv_alleles < 1 || n_snv_alleles > mchap::SNV_MAX_ALLELES)
+    return fail(MCHAP_ERR_BAD_ARG, "SNV posteriors: n_snv_alleles = %d not in 1..%d", n_snv_alleles, mchap::SNV_MAX_ALLELES);
+  if (n_pos < 1) return fail(MCHAP_ERR_BAD_ARG, "SNV posteriors: n_pos = %d, at least one SNV is needed", n_pos);
+  if (!cwr_fits(n_haps, ploidy)) return fail(MCHAP_ERR_LIMIT, "ploidy %d over %d haplotypes: more than 2^62 genotypes", ploidy, n_haps);
+  const long long G = host_cwr(n_haps, ploidy);
+  const int nblk = exact_nblk(G);
+  const int S = (int)host_cwr(n_snv_alleles, ploidy);
+  if ((long long)n_units * nblk > 0x7fffffffll) return fail(MCHAP_ERR_LIMIT, "SNV posteriors: %d units x %d tiles exceed one launch", n_units, nblk);
+  const long long nx = ((long long)n_pos * S + mchap::EXACT_THREADS - 1) / mchap::EXACT_THREADS;
+  if ((long long)n_units * nx > 0x7fffffffll) return fail(MCHAP_ERR_LIMIT, "SNV posteriors: %d units x %d SNVs exceed one launch", n_units, n_pos);
+  const SnvCarve cv = snv_carve(n_units, n_haps, ploidy, n_pos, n_snv_alleles);
+  if (!workspace || workspace_bytes < (int64_t)cv.bytes)
+    return fail(MCHAP_ERR_BAD_ARG, "workspace of %lld bytes is too small: %zu needed (mchap_exact_snv_workspace_bytes)",
+                (long long)workspace_bytes, cv.bytes);
+  const int chunk = mchap::exact_snv_chunk(n_haps, ploidy, S, n_pos);
+  if (chunk == 0) return fail(MCHAP_ERR_LIMIT, "n_haps %d too large for the SNV posteriors' prior tables", n_haps);
+  unsigned char *ws = reinterpret_cast<unsigned char *>(workspace);
+  double *norm = reinterpret_cast<double *>(ws + cv.norm);
+  // first pass: the normaliser of every unit's posterior -- its model evidence at its own F (one grid point)
+  int rc = mchap_exact_evidence_device(n_units, llks64, n_haps, ploidy, 1, inbreeding, unit_row, frequencies, stride, norm, ws + cv.ev,
+                                       (int64_t)(cv.norm - cv.ev), stream_);
+  if (rc) return rc;
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  mchap::ExactSnvParams E;
+  std::memset(&E, 0, sizeof(E));
+  E.llk64 = llks64;
+  E.inbreeding = inbreeding;
+  E.unit_row = unit_row;
+  E.freqs = frequencies;
+  E.hap_alleles = hap_alleles;
+  E.stride = stride;
+  E.H = n_haps; E.K = ploidy; E.M = n_pos; E.A = n_snv_alleles; E.S = S; E.nblk = nblk;
+  E.chunk = chunk;
+  E.G = G;
+  E.log_norm = norm;
+  E.part = reinterpret_cast<unsigned long long *>(ws + cv.part);
+  E.snv_post = snv_post;
+  E.log_norm_out = log_norm;
+  const size_t lds = mchap::exact_snv_lds(n_haps, ploidy, S, chunk);
+  auto k = ploidy <= 8 ? mchap::exact_snv_kernel<8> : mchap::exact_snv_kernel<mchap::EXACT_KMAX>;
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k, dim3((unsigned)((long long)n_units * nblk)), dim3(mchap::EXACT_THREADS), lds, stream, E);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(mchap::exact_snv_combine_kernel, dim3((unsigned)((long long)n_units * nx)), dim3(mchap::EXACT_THREADS), 0, stream, E);
+  HIP_TRY(hipGetLastError());
+  return MCHAP_OK;
+}
+
 // ---- host-pointer forms: one device allocation, copies in, the device entry point, copies out ----
 int mchap_exact_genotype_likelihoods(const double *reads, int n_reads, int n_pos, int max_allele,
                                      const int64_t *read_counts, const int8_t *haplotypes, int n_haps, int ploidy,

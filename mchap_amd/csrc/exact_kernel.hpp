@@ -1240,4 +1240,191 @@ static __global__ __launch_bounds__(64) void exact_evidence_combine_kernel(const
   }
 }
 
+// ---- SNV genotype posteriors over stored likelihoods (application.SnvCalls): snv_post[u][j][s] = sum_g p_u[g] [s_j(g) = s], the
+// unit's haplotype-genotype posterior p[g] = exp(llk[g] + log prior[g] - log_norm) added to the SNV genotype that g implies at
+// SNV j.  hap_alleles[h][j] is the SNV allele (0 .. A - 1, first appearance over the haplotypes) of haplotype h at SNV j; the
+// SNV genotype of g at j is the multiset of its K haplotypes' alleles, s_j(g) its rank in VCF order among the S = C(A + K - 1, K)
+// genotypes over A alleles.  log_norm is the model evidence of the unit at its own F (exact_evidence_kernel, one grid point): a
+// first pass.  The second pass adds every p[g] as a 64-bit fixed-point integer with SNV_FRACTION_BITS = 62 fraction bits,
+// q[g] = rint(p[g] * 2^62): integer addition is associative, so the LDS integer atomics, the tiles' sums and hence the result do
+// not depend on the order anything ran in -- equal inputs give equal bits.  The sum of all q stays below 2^63 (sum p = 1 up to the
+// rounding of log_norm).  Quantisation: |q[g] 2^-62 - p[g]| <= 2^-63, so an entry of snv_post is off by less than G * 2^-62
+// (1.2e-14 at 54 264 genotypes) plus the rounding of the final conversion to double (2^-53 relative). ----
+constexpr int SNV_FRACTION_BITS = 62;
+constexpr int SNV_MAX_ALLELES = 4;
+struct ExactSnvParams {
+  const double *llk64;        // [U][G] stored log likelihoods
+  const double *inbreeding;   // [U], or null: the flat genotype prior -log(G)
+  const int32_t *unit_row;    // [U] the unit's row of freqs and of hap_alleles
+  const double *freqs;        // [rows][stride] (not read under the flat prior)
+  const int8_t *hap_alleles;  // [rows][H][M]
+  int stride;
+  int H, K, M, A, S, nblk;
+  int chunk;                  // SNVs whose bins are in the LDS together (exact_snv_chunk)
+  long long G;
+  const double *log_norm;     // [U] the first pass' result
+  unsigned long long *part;   // [U][nblk][M][S] the tiles' fixed-point sums
+  double *snv_post;           // [U][M][S]
+  double *log_norm_out;       // [U] or null
+};
+// LDS: the prior tables of one F (lgd [H][K + 1], lgf, lfreq, left), the chunk's SNV alleles [H][chunk] as bytes, then ONE region
+// that first is the staging tile and, once every thread holds the fixed-point posteriors of its run in registers, the bins
+// [chunk][S] of 64-bit sums
+inline size_t exact_snv_lds(int H, int K, int S, int chunk) {
+  const size_t tile = (size_t)EXACT_THREADS * EXACT_EM_PITCH * 8, bins = (size_t)chunk * S * 8;
+  return ((size_t)H * (K + 1) + (K + 1) + H + 1) * 8 + (((size_t)H * chunk + 7) & ~(size_t)7) + (bins > tile ? bins : tile);
+}
+// SNVs per chunk: as many as keep the workgroup within 64 KB of LDS, at least one -- a single SNV may take the LDS up to 160 KB --,
+// 0 where not even one fits
+inline int exact_snv_chunk(int H, int K, int S, int M) {
+  if (exact_snv_lds(H, K, S, 1) > 160 * 1024) return 0;
+  int c = 1;
+  while (c < M && exact_snv_lds(H, K, S, c + 1) <= 64 * 1024) c++;
+  return c;
+}
+// Rank in VCF order of the SNV genotype with c[a] copies of allele a, the four counts packed one to a byte.  The ascending
+// genotype holds allele a at positions p_a .. q_a - 1 (p_a = c_0 + .. + c_{a-1}, q_a = p_a + c_a), and rank_genotype's sum of
+// C(a + i, i + 1) over those positions is C(a + q_a, a) - C(a + p_a, a).
+__device__ __forceinline__ int snv_rank(unsigned packed) {
+  const int c0 = packed & 255, c1 = (packed >> 8) & 255, c2 = (packed >> 16) & 255, c3 = packed >> 24;
+  const int p2 = c0 + c1, p3 = p2 + c2, q3 = p3 + c3;
+  auto t2 = [](int n) { return (n + 2) * (n + 1) / 2; };
+  auto t3 = [](int n) { return (n + 3) * (n + 2) * (n + 1) / 6; };
+  return c1 + (t2(p3) - t2(p2)) + (t3(q3) - t3(p3));
+}
+// One workgroup per (unit, tile of 4096 genotypes).  The tile is staged as exact_evidence_kernel stages it; each thread unranks
+// the first genotype of its run, walks it once with next_genotype for the fixed-point posteriors, and then once per SNV of every
+// chunk: the SNV alleles of the genotype's K haplotypes counted from the staged table, the counts ranked, and the posterior added
+// to that bin -- consecutive genotypes of a run that fall in the same bin are added in registers first, one atomic per change.
+template <int KM = 8>
+__global__ __launch_bounds__(EXACT_THREADS) void exact_snv_kernel(const ExactSnvParams P) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int unit = blockIdx.x / P.nblk, blk = blockIdx.x % P.nblk;
+  const int H = P.H, K = P.K, M = P.M, S = P.S, chunk = P.chunk;
+  const bool has_prior = P.inbreeding != nullptr;
+  double *lgd = reinterpret_cast<double *>(smem);  // [H][K + 1]
+  double *lgf = lgd + (size_t)H * (K + 1);         // [K + 1]
+  double *lfreq = lgf + (K + 1);                   // [H]
+  double *left = lfreq + H;                        // [1]
+  int8_t *ha = reinterpret_cast<int8_t *>(left + 1);  // [H][chunk]
+  double *tile = reinterpret_cast<double *>(ha + (((size_t)H * chunk + 7) & ~(size_t)7));  // [EXACT_THREADS][EXACT_EM_PITCH]
+  unsigned long long *bins = reinterpret_cast<unsigned long long *>(tile);                 // [chunk][S], after the tile
+  const int row = P.unit_row[unit];
+  const double *fr = has_prior ? P.freqs + (size_t)row * P.stride : nullptr;
+  const double F = has_prior ? P.inbreeding[unit] : 0.0;
+  const long long G = P.G;
+  const long long lo = (long long)blk * EXACT_GENOS_PER_BLOCK;
+  long long hi = lo + EXACT_GENOS_PER_BLOCK;
+  if (hi > G) hi = G;
+  const double *src = P.llk64 + (size_t)unit * G;
+#pragma unroll
+  for (int t = 0; t < EXACT_EM_RUN; t++) {
+    const int e = threadIdx.x + t * EXACT_THREADS;  // element of the tile: consecutive lanes, consecutive genotypes
+    if (lo + e < hi) tile[(e / EXACT_EM_RUN) * EXACT_EM_PITCH + (e % EXACT_EM_RUN)] = src[lo + e];
+  }
+  if (has_prior) {
+    // the prior tables of exact_setup, from the unit's F and its row
+    const double scale = (1.0 - F) / F;
+    for (int q = threadIdx.x; q < H * (K + 1); q += EXACT_THREADS) {
+      const int h = q / (K + 1), d = q % (K + 1);
+      const double alpha = fr[h] * scale;
+      lgd[q] = (F == 0.0 || d == 0) ? 0.0 : lgamma((double)d + alpha) - (lgamma((double)d + 1.0) + lgamma(alpha));
+    }
+    for (int d = threadIdx.x; d <= K; d += EXACT_THREADS) lgf[d] = lgamma((double)d + 1.0);
+    for (int h = threadIdx.x; h < H; h += EXACT_THREADS) lfreq[h] = fr[h];
+    if (threadIdx.x == 0) {
+      double sum_alpha = 0.0;
+      for (int h = 0; h < H; h++) sum_alpha += fr[h] * scale;
+      left[0] = (F == 0.0) ? 0.0 : (lgamma((double)K + 1.0) + lgamma(sum_alpha)) - lgamma((double)K + sum_alpha);
+    }
+  }
+  __syncthreads();
+  PriorTab pt;
+  pt.lgd = lgd;
+  pt.lgf = lgf;
+  pt.lfreq = lfreq;
+  pt.left = has_prior ? left[0] : 0.0;
+  pt.lnH = 0.0;
+  pt.F = F;
+  pt.has_freqs = 1;
+  const double norm = P.log_norm[unit];
+  const double flat = has_prior ? 0.0 : -log((double)G);
+  const long long first = lo + (long long)threadIdx.x * EXACT_EM_RUN;
+  lds_cdouble *mine = lds_table(tile) + threadIdx.x * EXACT_EM_PITCH;
+  int g[KM], g0[KM];
+#pragma unroll
+  for (int k = 0; k < KM; k++) g0[k] = 0;
+  if (first < hi) unrank_genotype(first, K, g0);
+  // the fixed-point posteriors of the thread's run (0 past the tile's end, for a genotype of probability 0 and for a unit
+  // without a finite genotype: its rows are set to NaN by exact_snv_combine_kernel)
+  unsigned long long q[EXACT_EM_RUN];
+#pragma unroll
+  for (int k = 0; k < KM; k++) g[k] = g0[k];
+#pragma unroll
+  for (int t = 0; t < EXACT_EM_RUN; t++) {
+    q[t] = 0;
+    if (first + t < hi) {
+      const double lj = mine[t] + (has_prior ? calling_log_prior(pt, g, K) : flat);
+      const double p = exp(lj - norm);
+      if (p > 0.0) q[t] = (unsigned long long)rint(fmin(ldexp(p, SNV_FRACTION_BITS), 9.0e18));  // (false for NaN)
+      next_genotype(g, K);
+    }
+  }
+  unsigned long long *out = P.part + ((size_t)unit * P.nblk + blk) * (size_t)M * S;
+  const int8_t *ua = P.hap_alleles + (size_t)row * H * M;
+  for (int j0 = 0; j0 < M; j0 += chunk) {
+    const int mc = (M - j0 < chunk) ? M - j0 : chunk;
+    __syncthreads();  // (the tile has been read; later: the bins of the chunk before have been written out)
+    for (int i = threadIdx.x; i < mc * S; i += EXACT_THREADS) bins[i] = 0;
+    for (int i = threadIdx.x; i < H * mc; i += EXACT_THREADS) {
+      const int h = i / mc, c = i % mc;
+      const int a = ua[(size_t)h * M + j0 + c];
+      ha[i] = (int8_t)(a < 0 ? 0 : (a >= P.A ? P.A - 1 : a));  // (a value outside the table's range cannot leave the bins)
+    }
+    __syncthreads();
+    for (int c = 0; c < mc; c++) {
+      unsigned long long *bin = bins + (size_t)c * S;
+      int cur = -1;
+      unsigned long long acc = 0;
+#pragma unroll
+      for (int k = 0; k < KM; k++) g[k] = g0[k];
+#pragma unroll
+      for (int t = 0; t < EXACT_EM_RUN; t++) {
+        if (first + t < hi) {
+          unsigned packed = 0;
+#pragma unroll
+          for (int k = 0; k < KM; k++)
+            if (k < K) packed += 1u << (8 * ha[g[k] * mc + c]);
+          const int s = snv_rank(packed);
+          if (s != cur) {
+            if (acc) atomicAdd(bin + cur, acc);
+            cur = s;
+            acc = 0;
+          }
+          acc += q[t];
+          next_genotype(g, K);
+        }
+      }
+      if (acc) atomicAdd(bin + cur, acc);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < mc * S; i += EXACT_THREADS) out[(size_t)j0 * S + i] = bins[i];
+  }
+}
+// The tiles of a unit summed (integers: any order gives the same sum) and scaled back to a probability; NaN for a unit without a
+// finite genotype.
+static __global__ __launch_bounds__(EXACT_THREADS) void exact_snv_combine_kernel(const ExactSnvParams P) {
+  const size_t MS = (size_t)P.M * P.S;
+  const unsigned nx = (unsigned)((MS + EXACT_THREADS - 1) / EXACT_THREADS);  // workgroups of a unit
+  const int unit = blockIdx.x / nx, bx = blockIdx.x % nx;
+  const double norm = P.log_norm[unit];
+  if (P.log_norm_out && bx == 0 && threadIdx.x == 0) P.log_norm_out[unit] = norm;
+  const size_t i = (size_t)bx * EXACT_THREADS + threadIdx.x;
+  if (i >= MS) return;
+  const unsigned long long *part = P.part + (size_t)unit * P.nblk * MS;
+  unsigned long long sum = 0;
+  for (int b = 0; b < P.nblk; b++) sum += part[(size_t)b * MS + i];
+  P.snv_post[(size_t)unit * MS + i] = (norm > -INFINITY && norm < INFINITY) ? ldexp((double)sum, -SNV_FRACTION_BITS) : NAN;
+}
+
 }  // namespace mchap

@@ -729,6 +729,73 @@ class ExactModelEvidence:
         return out
 
 
+class ExactSnvPosteriors:
+    """SNV genotype posteriors of exact-caller units whose likelihoods are resident on the device
+    (mchap_exact_snv_posteriors_device): for every unit and SNV the unit's haplotype-genotype posterior summed over the SNV genotype
+    each haplotype genotype implies there."""
+
+    MAX_SNV_ALLELES = 4
+
+    def __init__(self, device=None):
+        self.torch = _torch()
+        self.device = _device(self.torch, device)
+        self.launches = 0   # groups enqueued
+        self.log_norm = None   # the normalisers [U] of the last group, on the device
+
+    _tensor = ExactModelEvidence._tensor
+
+    def add_group(self, llks64, n_haps, ploidy, inbreeding, unit_row, freqs, hap_alleles):
+        """The units of one shape (n_haps, ploidy), enqueued on torch's current stream: llks64 a float64 torch tensor [U * G] on
+        the device; inbreeding [U] (or a scalar for all units), every F in [0, 1) -- checked here, on the host copy --, or None: the
+        flat genotype prior, freqs not used; unit_row [U]: each unit's row of freqs [rows, stride >= n_haps] and of hap_alleles
+        int8 [rows, n_haps, M], the SNV allele of every haplotype at every SNV (0 .. 3, checked here).  Returns the float64 tensor
+        [U, M, S] on the device, S = C(A + ploidy - 1, ploidy) for A the largest number of SNV alleles in hap_alleles."""
+        torch, dev = self.torch, self.device
+        H, K = int(n_haps), int(ploidy)
+        if K < 1 or K > _lib.MAX_PLOIDY_GENERAL or comb(H + K - 1, K) >= 1 << 62:
+            raise NotImplementedError("mchap_hip: ploidy %d over %d haplotypes is beyond this build's exact caller" % (K, H))
+        G = comb(H + K - 1, K)
+        assert llks64.dtype == torch.float64 and llks64.is_contiguous() and llks64.numel() % G == 0
+        U = llks64.numel() // G
+        ha = np.ascontiguousarray(hap_alleles, dtype=np.int8)
+        if ha.ndim != 3 or ha.shape[1] != H or ha.shape[2] < 1:
+            raise ValueError("hap_alleles: [rows, %d, M] with M >= 1, got %r" % (H, ha.shape))
+        if ha.size and (int(ha.min()) < 0 or int(ha.max()) >= self.MAX_SNV_ALLELES):
+            raise ValueError("hap_alleles: every SNV allele must lie in 0..%d" % (self.MAX_SNV_ALLELES - 1))
+        M, A = int(ha.shape[2]), int(ha.max()) + 1 if ha.size else 1
+        S = comb(A + K - 1, K)
+        rows = np.ascontiguousarray(unit_row, dtype=np.int32)
+        assert rows.shape == (U,) and (U == 0 or (int(rows.min()) >= 0 and int(rows.max()) < ha.shape[0]))
+        d_F = d_fr = None
+        stride = 0
+        if inbreeding is not None:
+            F = np.array(np.broadcast_to(np.asarray(inbreeding, dtype=np.float64), (U,)))
+            if not np.all((F >= 0.0) & (F < 1.0)):   # (False for NaN and infinities too)
+                raise ValueError("inbreeding: every F must lie in [0, 1)")
+            d_F = torch.from_numpy(F).to(dev)
+            d_fr = self._tensor(freqs, torch.float64, np.float64)
+            assert d_fr.dim() == 2 and (U == 0 or int(rows.max()) < int(d_fr.shape[0]))
+            stride = int(d_fr.shape[1])
+        out = torch.empty((U, M, S), dtype=torch.float64, device=dev)
+        self.log_norm = torch.empty(U, dtype=torch.float64, device=dev)
+        if U == 0:
+            return out
+        L = _lib.lib()
+        wsb = int(L.mchap_exact_snv_workspace_bytes(U, H, K, M, A))
+        free, _ = torch.cuda.mem_get_info()
+        if wsb < 0 or wsb > free:
+            raise NotImplementedError("mchap_hip: SNV posteriors of %d units of ploidy %d over %d haplotypes: the workspace does not "
+                                      "fit the device" % (U, K, H))
+        d_row = torch.from_numpy(rows).to(dev)
+        d_ha = torch.from_numpy(ha.reshape(-1)).to(dev)
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+        _lib.check(L.mchap_exact_snv_posteriors_device(
+            U, _ptr(llks64), H, K, M, A, _ptr(d_F), _ptr(d_row), _ptr(d_fr), stride, _ptr(d_ha), _ptr(out), _ptr(self.log_norm),
+            _ptr(ws), C.c_int64(wsb), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        self.launches += 1
+        return out
+
+
 class DenovoRaggedBatch(_OwnBuffers):
     """Units of different shapes (loci with different numbers of SNVs and alleles, samples with different read depths,
     per-sample ploidy / inbreeding) in ONE sampler launch, with the posterior summary and the replicate incongruence

@@ -156,16 +156,21 @@ def read_vcf(path):
         if line.startswith("#"):
             samples = f[9:]
             continue
-        info = {}
-        for kv in f[7].split(";"):
-            if "=" in kv:
-                k, v = kv.split("=", 1)
-                info[k] = v
-            else:
-                info[kv] = True
-        out.append(dict(chrom=f[0], pos=int(f[1]), id=f[2], ref=f[3], alts=() if f[4] == "." else tuple(f[4].split(",")),
-                        info=info, format=f[8] if len(f) > 8 else "", samples=dict(zip(samples, f[9:]))))
+        out.append(vcf_record(f, samples))
     return samples, out
+
+
+def vcf_record(f, samples):
+    """The record dict of read_vcf from the tab-separated fields of a record line."""
+    info = {}
+    for kv in f[7].split(";"):
+        if "=" in kv:
+            k, v = kv.split("=", 1)
+            info[k] = v
+        else:
+            info[kv] = True
+    return dict(chrom=f[0], pos=int(f[1]), id=f[2], ref=f[3], alts=() if f[4] == "." else tuple(f[4].split(",")),
+                info=info, format=f[8] if len(f) > 8 else "", samples=dict(zip(samples, f[9:])))
 
 
 _FILTER_OPS = {"=": np.equal, "==": np.equal, "!=": np.not_equal, ">": np.greater, ">=": np.greater_equal,
