@@ -413,6 +413,33 @@ int mchap_exact_snv_posteriors_device(int n_units, const double *llks64, int n_h
                                       const int8_t *hap_alleles, double *snv_post, double *log_norm, void *workspace,
                                       int64_t workspace_bytes, void *stream);
 
+/* Expected read depth of every haplotype (call-exact --allele-depths): for every unit u, read row r and haplotype h
+ *   post[u][r][h] = sum_g p_u[g] c_h(g) P[r][h] / D(r, g),   D(r, g) = sum_h c_h(g) P[r][h],   depth[u][h] = sum_r w_r post[u][r][h],
+ * p_u[g] = exp(llk_u[g] + log prior_u[g] - log_norm[u]) the unit's genotype posterior under the calling prior (as the SNV
+ * posteriors: inbreeding[u] and row unit_row[u] of `frequencies`; inbreeding = NULL: the flat genotype prior, unit_row and
+ * frequencies not read), c_h(g) the dosage of haplotype h in genotype g, P[r][h] the product over the non-NaN cells
+ * reads[r][j][haplotypes[h][j]], w_r = read_counts[u][r] (NULL: 1).  A pair (g, r) contributes only where p[g] > 0 and w_r > 0,
+ * and 0 where D is 0 nevertheless; a row of weight 0 is exactly 0.  reads [U][n_reads][n_pos][max_allele], read_counts
+ * [U][n_reads], haplotypes [U][n_haps][n_pos] and llks64 [U][G] are what mchap_exact_call_batch_device took and left.
+ * depth [U][n_haps]; read_post [U][n_reads][n_haps] (may be NULL: the rows are then summed inside the workgroups and the
+ * workspace is n_reads times smaller); log_norm [U] (may be NULL): the normaliser, the unit's model evidence at its own F.  A unit
+ * without a finite genotype gives NaN everywhere (log_norm -inf).
+ * Two passes: the evidence launches for log_norm, then one workgroup per (unit, tile of 4096 genotypes) walks the genotypes with
+ * p > 0 with one lane per read row, every accumulator cell owned by one lane; the tiles are summed in tile order.  Equal inputs
+ * give equal bits whatever the order of the units.  The read rows are worked in tiles of mchap_exact_support_tile rows (a multiple
+ * of 64: as many as keep a workgroup within 64 KB of LDS, a single tile of 64 may take up to 160 KB; 0: not even that fits -- the
+ * call is MCHAP_ERR_LIMIT), so n_reads has no upper bound.  `workspace`: mchap_exact_support_workspace_bytes (per_read: whether
+ * read_post is asked for; -1: a ploidy outside 1..MCHAP_MAX_PLOIDY_DENOVO or more than 2^62 genotypes -- the call itself is
+ * MCHAP_ERR_LIMIT).  Every F must lie in [0, 1): the arrays are on the device, so that is the caller's duty
+ * (device.ExactReadSupport checks its host copy).  Enqueues on `stream`, no synchronisation. */
+int64_t mchap_exact_support_workspace_bytes(int n_units, int n_reads, int n_haps, int ploidy, int per_read);
+int mchap_exact_support_tile(int n_reads, int n_haps, int ploidy);
+int mchap_exact_allele_support_device(int n_units, const double *reads, int n_reads, int n_pos, int max_allele,
+                                      const int64_t *read_counts, const int8_t *haplotypes, int n_haps, int ploidy,
+                                      const double *llks64, const double *inbreeding, const int32_t *unit_row,
+                                      const double *frequencies, int stride, double *depth, double *read_post, double *log_norm,
+                                      void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Summaries of given posterior arrays [U][G] (calling.exact.posterior_allele_frequencies 332-369, the sum of
  * alternate_dosage_posteriors 372-407 for the array's mode): device pointers, any output may be NULL. */
 int mchap_exact_posterior_summaries_batch_device(int n_units, const double *posteriors, int64_t n_genotypes, int ploidy,

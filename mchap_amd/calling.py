@@ -14,6 +14,7 @@ from . import _lib
 __all__ = [
     "posterior_mode",
     "posterior_mode_batch",
+    "allele_read_support",
     "genotype_likelihoods",
     "genotype_posteriors",
     "posterior_allele_frequencies",
@@ -204,6 +205,32 @@ def posterior_mode(reads, ploidy, haplotypes, read_counts=None, prior=None, retu
     if return_posterior_occurrence:
         res.append(out[k][0])
     return tuple(res)
+
+
+def allele_read_support(reads, ploidy, haplotypes, read_counts=None, prior=None, per_read=False):
+    """Expected read depth of every haplotype of one unit (not a reference function; the definition: application.allele_support_unit):
+    depth float64 [H], the responsibility of haplotype h for every read under every genotype, averaged over the genotype posterior
+    and summed over the reads with their weights -- sum(depth) is the unit's read weight.  reads [R, M, A], haplotypes [H, M],
+    read_counts [R] or None, prior = None (the flat genotype prior) | (inbreeding, frequencies None | [H]).  per_read=True:
+    (depth, read_post float64 [R, H]), every row of a read with weight summing to 1.  NaN where no genotype is finite."""
+    import torch
+
+    from .device import ExactDeviceBatch, ExactReadSupport
+
+    haps = np.ascontiguousarray(haplotypes, dtype=np.int8)
+    if len(reads) == 0:   # (no reads: nothing to assign)
+        return (np.zeros(len(haps)), np.zeros((0, len(haps)))) if per_read else np.zeros(len(haps))
+    reads, rc = _reads(reads, read_counts)
+    batch = ExactDeviceBatch(reads[None], int(ploidy), haps[None], None if rc is None else rc[None], None, cache_joint=False)
+    F = fr = None
+    if prior is not None:
+        F = [float(prior[0])]
+        fr = np.full((1, len(haps)), 1.0 / len(haps)) if prior[1] is None else np.asarray(prior[1], dtype=np.float64).reshape(1, -1)
+    got = ExactReadSupport(batch.device).add_group(batch, batch.run_llks64(), F, [0], fr, per_read=per_read)
+    torch.cuda.synchronize()
+    if per_read:
+        return got[0].cpu().numpy()[0], got[1].cpu().numpy()[0]
+    return got.cpu().numpy()[0]
 
 
 def call_arrays_batch(reads, ploidy, haplotypes, read_counts=None, prior=None, return_arrays=True):

@@ -15,7 +15,8 @@ sharded over the ranks and rank 0 writes the one VCF; `--reference` may name a F
 also writes a table of every sample's log evidence under candidate (ploidy, inbreeding) pairs (application.ModelEvidence) and leaves
 the VCF, header included, as it is without those flags; so does `call-exact --snv-calls FILE [--snv-report GP]`, which writes the
 SNV-level VCF `atomize` would make of the run's output with GQ, DS and ACP from the exact SNV genotype posteriors
-(application.SnvCalls).  `atomize --haplotypes FILE` is host only (mchap_amd/atomize.py)."""
+(application.SnvCalls), and `call-exact --allele-depths FILE`, which writes the run's VCF again with ADP, the posterior expected read
+depth of every allele (application.AlleleDepths).  `atomize --haplotypes FILE` is host only (mchap_amd/atomize.py)."""
 import argparse
 import sys
 
@@ -160,6 +161,10 @@ def build_parser(program):
                            help="(not a reference flag) write to FILE, when the run ends, the SNV-level VCF `atomize` would make of this "
                                 "run's output (one record per basis SNV, GT:GQ:PQ:DP:DS), with GQ, DS and INFO/ACP from the exact SNV "
                                 "genotype posteriors")
+            p.add_argument("--allele-depths", type=str, nargs=1, default=[None], metavar="FILE",
+                           help="(not a reference flag) write to FILE, when the run ends, this run's VCF with one field added: ADP, the "
+                                "posterior expected read depth of every allele (FORMAT per sample, INFO their sum; Number=R, so FILE "
+                                "serves as --haplotypes with --filter-input-haplotypes \"ADP>=1\")")
             p.add_argument("--snv-report", type=str, nargs="+", default=None, metavar="FIELD", choices=["GP"],
                            help="(not a reference flag) with --snv-calls: GP adds the SNV genotype posteriors as a sixth FORMAT field")
     p.add_argument("--report", type=str, nargs="*", default=[],
@@ -226,7 +231,7 @@ def run(argv, out=None):
                                     read_group_field=id_field, mapping_quality=args.mapping_quality[0],
                                     skip_duplicates=args.skip_duplicates, skip_qcfail=args.skip_qcfail,
                                     skip_supplementary=args.skip_supplementary, workers=args.cores[0])
-    seed = evidence = snv_calls = None
+    seed = evidence = snv_calls = allele_depths = header = None
     block_path = BLOCK_PATHS[args.block_path]
     if program == "assemble":
         if args.targets[0] is not None and args.region[0] is not None:
@@ -265,11 +270,15 @@ def run(argv, out=None):
                                  "frequencies to estimate")
             evidence = model_evidence_settings(args, samples, inbreeding, tag, estimate, world)
             snv_calls = snv_calls_settings(args, samples, world, ["mchap_amd"] + header_argv)
+            if args.allele_depths[0] is not None:
+                header = vcfheader.header_lines(program, ["mchap_amd"] + header_argv, samples, contigs, report=report, random_seed=seed,
+                                                estimate=estimate is not None)
+            allele_depths = allele_depths_settings(args, samples, world, header)
             records = application.call_exact(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
                                              inbreeding=inbreeding, filter_input_haplotypes=args.filter_input_haplotypes[0], shard=shard,
                                              block_path=block_path, estimate_frequencies=estimate,
                                              estimate_tolerance=1e-6 if args.estimate_tolerance[0] is None else args.estimate_tolerance[0],
-                                             model_evidence=evidence, snv_calls=snv_calls)
+                                             model_evidence=evidence, snv_calls=snv_calls, allele_depths=allele_depths)
         else:
             seed = args.mcmc_seed[0]
             records = application.call(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
@@ -286,8 +295,10 @@ def run(argv, out=None):
         if rank != 0:
             return n_mine
         lines = [ln for part in gathered for ln in part]
-    for line in vcfheader.header_lines(program, ["mchap_amd"] + header_argv, samples, contigs, report=report, random_seed=seed,
-                                      estimate=program == "call-exact" and args.estimate_prior_frequencies[0] is not None):
+    if header is None:   # (--allele-depths has formed it already: its file carries the very same lines)
+        header = vcfheader.header_lines(program, ["mchap_amd"] + header_argv, samples, contigs, report=report, random_seed=seed,
+                                        estimate=program == "call-exact" and args.estimate_prior_frequencies[0] is not None)
+    for line in header:
         out.write(line + "\n")
     n = 0
     run.limit_records = 0
@@ -300,16 +311,20 @@ def run(argv, out=None):
         evidence.write(args.model_evidence[0])
     if snv_calls is not None:
         snv_calls.write(args.snv_calls[0])
+    if allele_depths is not None:
+        allele_depths.write(args.allele_depths[0])
     return n
 
 
 EVIDENCE_FLAGS = ("--model-evidence", "--evidence-ploidy", "--evidence-inbreeding")
 # the flags of the SNV file: left out of the header's command line as the evidence flags are
 SNV_FLAGS = ("--snv-calls", "--snv-report")
+# ... and the flag of the allele-depths file
+ALLELE_DEPTH_FLAGS = ("--allele-depths",)
 
 
 def _header_argv(argv, options):
-    """The command line as the VCF header states it: without the model-evidence and SNV-file flags and their values -- the VCF, header included,
+    """The command line as the VCF header states it: without the model-evidence, SNV-file and allele-depths flags and their values -- the VCF, header included,
     is byte for byte what the run writes without them.  options: the parser's option strings; a flag is resolved as argparse
     resolves it (the exact name, else the one option it is a prefix of), so an abbreviated flag is taken out too."""
     out, skipping = [], False
@@ -317,7 +332,7 @@ def _header_argv(argv, options):
         if a.startswith("--"):
             name = a.split("=", 1)[0]
             full = [name] if name in options else [o for o in options if o.startswith(name)]
-            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS + SNV_FLAGS
+            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS + SNV_FLAGS + ALLELE_DEPTH_FLAGS
         if not skipping:
             out.append(a)
     return out
@@ -358,6 +373,17 @@ def snv_calls_settings(args, samples, world, command):
     if world > 1:
         raise ValueError("--snv-calls runs as a single process: the SNV file is not gathered from several ranks (WORLD_SIZE > 1)")
     return application.SnvCalls(samples, atomize.vcf_contig_lines(args.haplotypes[0]), report=args.snv_report or (), command=command)
+
+
+def allele_depths_settings(args, samples, world, header_lines):
+    """The --allele-depths flag of call-exact -> an application.AlleleDepths over the run's header lines, or None without it."""
+    from . import application
+
+    if args.allele_depths[0] is None:
+        return None
+    if world > 1:
+        raise ValueError("--allele-depths runs as a single process: the file is not gathered from several ranks (WORLD_SIZE > 1)")
+    return application.AlleleDepths(samples, header_lines)
 
 
 def _run_atomize(argv, args, out):

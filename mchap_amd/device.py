@@ -796,6 +796,66 @@ class ExactSnvPosteriors:
         return out
 
 
+class ExactReadSupport:
+    """Expected read depth of every haplotype for exact-caller units whose reads and likelihoods are resident on the device
+    (mchap_exact_allele_support_device): the responsibility of every haplotype for every read under every genotype, averaged over
+    the unit's genotype posterior and summed over the reads with their weights."""
+
+    def __init__(self, device=None):
+        self.torch = _torch()
+        self.device = _device(self.torch, device)
+        self.launches = 0      # groups enqueued
+        self.log_norm = None   # the normalisers [U] of the last group, on the device
+
+    _tensor = ExactModelEvidence._tensor
+
+    def add_group(self, batch, llks64, inbreeding, unit_row, freqs, per_read=False):
+        """The units of an ExactDeviceBatch -- its reads, haplotypes and read counts are on the device already --, enqueued on
+        torch's current stream: llks64 the batch's float64 likelihoods [U * G] (run_llks64); inbreeding [U] (or a scalar for all
+        units), every F in [0, 1) -- checked here, on the host copy --, or None: the flat genotype prior, unit_row and freqs not
+        used; unit_row [U]: each unit's row of freqs [rows, stride >= n_haps].  Returns the float64 tensor depth [U, H] on the
+        device -- with per_read=True the pair (depth, read_post [U, R, H]).  A shape the library refuses (ploidy, genotype count,
+        tables beyond the LDS, a workspace beyond the device): NotImplementedError."""
+        torch, dev = self.torch, self.device
+        U, R, M, A, H, K = batch.shape
+        if K < 1 or K > _lib.MAX_PLOIDY_GENERAL or comb(H + K - 1, K) >= 1 << 62:
+            raise NotImplementedError("mchap_hip: ploidy %d over %d haplotypes is beyond this build's exact caller" % (K, H))
+        assert llks64.dtype == torch.float64 and llks64.is_contiguous() and llks64.numel() == U * batch.G
+        L = _lib.lib()
+        if U and int(L.mchap_exact_support_tile(R, H, K)) == 0:
+            raise NotImplementedError("mchap_hip: allele support over %d haplotypes: not even 64 read rows of its tables fit the LDS" % H)
+        d_F = d_fr = d_row = None
+        stride = 0
+        if inbreeding is not None:
+            F = np.array(np.broadcast_to(np.asarray(inbreeding, dtype=np.float64), (U,)))
+            if not np.all((F >= 0.0) & (F < 1.0)):   # (False for NaN and infinities too)
+                raise ValueError("inbreeding: every F must lie in [0, 1)")
+            rows = np.ascontiguousarray(unit_row, dtype=np.int32)
+            d_fr = self._tensor(freqs, torch.float64, np.float64)
+            assert d_fr.dim() == 2 and int(d_fr.shape[1]) >= H
+            assert rows.shape == (U,) and (U == 0 or (int(rows.min()) >= 0 and int(rows.max()) < int(d_fr.shape[0])))
+            stride = int(d_fr.shape[1])
+            d_F = torch.from_numpy(F).to(dev)
+            d_row = torch.from_numpy(rows).to(dev)
+        depth = torch.empty((U, H), dtype=torch.float64, device=dev)
+        self.log_norm = torch.empty(U, dtype=torch.float64, device=dev)
+        if U == 0:
+            return (depth, torch.empty((0, R, H), dtype=torch.float64, device=dev)) if per_read else depth
+        wsb = int(L.mchap_exact_support_workspace_bytes(U, R, H, K, 1 if per_read else 0))
+        free, _ = torch.cuda.mem_get_info()
+        if wsb < 0 or wsb + (U * R * H * 8 if per_read else 0) > free:
+            raise NotImplementedError("mchap_hip: allele support of %d units of ploidy %d over %d haplotypes: the workspace does not "
+                                      "fit the device" % (U, K, H))
+        post = torch.empty((U, R, H), dtype=torch.float64, device=dev) if per_read else None
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+        _lib.check(L.mchap_exact_allele_support_device(
+            U, _ptr(batch.d_reads), R, M, A, _ptr(batch.d_counts), _ptr(batch.d_haps), H, K, _ptr(llks64), _ptr(d_F), _ptr(d_row),
+            _ptr(d_fr), stride, _ptr(depth), _ptr(post), _ptr(self.log_norm), _ptr(ws), C.c_int64(wsb),
+            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        self.launches += 1
+        return (depth, post) if per_read else depth
+
+
 class DenovoRaggedBatch(_OwnBuffers):
     """Units of different shapes (loci with different numbers of SNVs and alleles, samples with different read depths,
     per-sample ploidy / inbreeding) in ONE sampler launch, with the posterior summary and the replicate incongruence
