@@ -440,6 +440,45 @@ int mchap_exact_allele_support_device(int n_units, const double *reads, int n_re
                                       const double *frequencies, int stride, double *depth, double *read_post, double *log_norm,
                                       void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Progeny calls under their parents' cross prior (call-exact --cross-calls).  Per record with n_haps haplotypes, parents P and Q of
+ * even ploidies, gametes of t = ploidy / 2 haplotypes, progeny of ploidy t_P + t_Q; multisets in VCF order, like genotypes.
+ *   gametes[u][a]  = (1 - e_u) (sum_{g = a + r} p_u[g] prod_h C(c_h(g), a_h)) / C(K, t) + e_u Mult(a; t, f),
+ *   log_cross[r][gc] = log sum_{a in gc, |a| = t_P} gametes_p[r][a] gametes_q[r][gc - a],
+ *   posterior[u][gc] = exp(llk_u[gc] + log_cross[unit_row[u]][gc] - log_z[u]).
+ * p_u[g] = exp(llk_u[g] + log prior_u[g] - log_norm[u]) is the parent unit's genotype posterior under the calling prior (as the
+ * SNV posteriors and the allele support: inbreeding[u] and row unit_row[u] of `frequencies`; inbreeding = NULL: the flat genotype
+ * prior), c_h(g) the dosage of haplotype h in g and a_h that in a; the sum runs over the C(H + K - t - 1, K - t) complements r of a
+ * in VCF order of r.  e_u = gamete_error[u] mixes in Mult, the multinomial pmf of a under f, the unit's row of `frequencies` --
+ * always read, under the flat genotype prior too.  The cross sum runs over the distinct sub-multisets a of gc in VCF order of a;
+ * an entry of log_cross is exactly -inf where every product is 0.  No double reduction; the two parents are independent tables.
+ * gametes [U][C(H + t - 1, t)], log_norm [U] (may be NULL); a parent without a finite genotype gives NaN gametes (log_norm -inf),
+ * NaN in its row of log_cross, and a NaN log_z.  gametes_p / gametes_q [rows][.] and log_cross [rows][G_c] are per record: every
+ * progeny of the record shares the row.  The gamete tables of a row are staged in LDS where both fit 64 KB and read from global
+ * memory otherwise: a large n_haps is slower, never refused.
+ * The posterior call streams llks64 [U][G_c] + log_cross in tiles of 4096 genotypes, tiles combined in tile order: log_z [U] the
+ * cross evidence, mode [U] the first maximum in VCF order (-1 where log_z is not finite: NaN, or -inf where no genotype has a
+ * finite term), mode_prob [U] its probability (NaN then), posteriors [U][G_c] (may be NULL), and -- where log_norm is not NULL --
+ * log_norm [U], the unit's evidence under its own calling prior (inbreeding, freq_row, frequencies, stride as
+ * mchap_exact_evidence_device takes them), so that log_z - log_norm is the log Bayes factor of the cross against the population.
+ * All three are gather-form: every output cell has one owning lane and a fixed summation order, no atomics; equal inputs give
+ * equal bits whatever the order of the units.  `workspace`: the *_workspace_bytes of the call (the cross prior needs none; -1: a
+ * ploidy outside 1..MCHAP_MAX_PLOIDY_DENOVO, an odd parent, or more than 2^62 genotypes -- the call itself is MCHAP_ERR_LIMIT, an
+ * odd parent MCHAP_ERR_BAD_ARG).  Every F must lie in [0, 1) and every e in [0, 1]: the arrays are on the device, so that is the
+ * caller's duty (device.ExactCross checks its host copies).  Enqueue on `stream`, no synchronisation. */
+int64_t mchap_exact_gametes_workspace_bytes(int n_units, int n_haps, int ploidy);
+int mchap_exact_gametes_device(int n_units, const double *llks64, int n_haps, int ploidy, const double *inbreeding,
+                               const int32_t *unit_row, const double *frequencies, int stride, const double *gamete_error,
+                               double *gametes, double *log_norm, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t mchap_exact_cross_prior_workspace_bytes(int n_rows, int n_haps, int ploidy_p, int ploidy_q);
+int mchap_exact_cross_prior_device(int n_rows, const double *gametes_p, const double *gametes_q, int n_haps, int ploidy_p,
+                                   int ploidy_q, double *log_cross, void *stream);
+int64_t mchap_exact_cross_posterior_workspace_bytes(int n_units, int n_haps, int ploidy);
+int mchap_exact_cross_posterior_device(int n_units, const double *llks64, int n_haps, int ploidy, const double *log_cross,
+                                       const int32_t *unit_row, const double *inbreeding, const int32_t *freq_row,
+                                       const double *frequencies, int stride, double *log_z, int64_t *mode, double *mode_prob,
+                                       double *log_norm, double *posteriors, void *workspace, int64_t workspace_bytes,
+                                       void *stream);
+
 /* Summaries of given posterior arrays [U][G] (calling.exact.posterior_allele_frequencies 332-369, the sum of
  * alternate_dosage_posteriors 372-407 for the array's mode): device pointers, any output may be NULL. */
 int mchap_exact_posterior_summaries_batch_device(int n_units, const double *posteriors, int64_t n_genotypes, int ploidy,

@@ -1175,6 +1175,367 @@ class AlleleDepths:
             fh.write(self.text())
 
 
+# ---------------------------------------------------------------------------------------------------------
+# call-exact --cross-calls: the run's own VCF with the progeny of one cross called under their parents' cross prior
+# ---------------------------------------------------------------------------------------------------------
+def _multiset_ranks(g):
+    """int64 [N]: the VCF index of every ascending multiset g [N, k] (jitutils.py:253-276: sum_i C(g_i + i, i + 1))."""
+    from math import comb
+
+    g = np.asarray(g, dtype=np.int64)
+    k = g.shape[1]
+    top = int(g.max()) + 1 if g.size else 1
+    tab = np.array([[comb(n + i, i + 1) for i in range(k)] for n in range(top)], dtype=np.int64).reshape(top, k)
+    return tab[g, np.arange(k)[None, :]].sum(axis=1)
+
+
+def _dosages(g, H):
+    """int64 [N, H]: the dosage of every haplotype in the multisets g [N, k]."""
+    d = np.zeros((len(g), H), dtype=np.int64)
+    for k in range(g.shape[1]):
+        np.add.at(d, (np.arange(len(g)), g[:, k]), 1)
+    return d
+
+
+def gamete_table(p, H, K, f, error):
+    """float64 [C(H + t - 1, t)], t = K / 2: the gamete distribution of a parent of even ploidy K with genotype posterior p [G]
+    (VCF order), without double reduction, mixed with the multinomial of the frequencies f [H] at the gamete error:
+        gam[a]  = (sum_{g = a + r} p[g] prod_h C(c_h(g), a_h)) / C(K, t)      over the complements r of a, in VCF order of r
+        gam'[a] = (1 - error) gam[a] + error Mult(a; t, f)
+    (reference mchap/assemble/inheritence.py gamete_probabilities, mchap/pedigree/prior.py gamete_log_pmf with lambda = 0 and
+    log_unknown_dosage_prior).  The order of every sum and product is the kernel's (exact_gamete_kernel)."""
+    from math import comb, factorial
+
+    if K < 2 or K % 2:
+        raise ValueError("a parent of ploidy %d: the gametes of an even ploidy alone are formed" % K)
+    t = K // 2
+    p = np.asarray(p, dtype=np.float64)
+    f = np.asarray(f, dtype=np.float64)
+    a = _genotype_table(H, t)
+    comp = _genotype_table(H, K - t)
+    da, dr = _dosages(a, H), _dosages(comp, H)
+    binom = np.array([[comb(n, k) for k in range(K + 1)] for n in range(K + 1)], dtype=np.int64)
+    total = np.zeros(len(a))
+    for c in range(len(comp)):
+        g = np.sort(np.concatenate([a, np.broadcast_to(comp[c], (len(a), K - t))], axis=1), axis=1)
+        w = np.prod(binom[da + dr[c][None, :], da], axis=1)
+        pg = p[_multiset_ranks(g)]
+        total += np.where(pg > 0.0, pg, 0.0) * w
+    gam = total / comb(K, t)
+    coef = np.array([factorial(t) // int(np.prod([factorial(int(x)) for x in row])) for row in da], dtype=np.float64)
+    pf = np.ones(len(a))
+    for i in range(t):
+        pf = pf * f[a[:, i]]
+    return (1.0 - error) * gam + error * (coef * pf)
+
+
+def cross_prior_tables(p_p, K_p, p_q, K_q, H, gamete_error=(0.0, 0.0), f=None):
+    """(gam_p, gam_q, X): the gamete tables (gamete_table) of parents with genotype posteriors p_p, p_q and even ploidies K_p, K_q
+    over H haplotypes, and the distribution of their cross over the C(H + K_c - 1, K_c) genotypes of ploidy K_c = K_p / 2 + K_q / 2,
+        X[gc] = sum_{a in gc, |a| = K_p / 2} gam_p[a] gam_q[gc - a]            over the distinct sub-multisets a, in VCF order of a
+    (reference cross_probabilities; trio_log_pmf with lambda = 0).  f None: flat frequencies."""
+    from math import comb
+
+    f = np.full(H, 1.0 / H) if f is None else np.asarray(f, dtype=np.float64)
+    gam_p = gamete_table(p_p, H, K_p, f, float(gamete_error[0]))
+    gam_q = gamete_table(p_q, H, K_q, f, float(gamete_error[1]))
+    tp, tq = K_p // 2, K_q // 2
+    a, b = _genotype_table(H, tp), _genotype_table(H, tq)
+    X = np.zeros(comb(H + tp + tq - 1, tp + tq))
+    for i in range(len(a)):   # (for one a the genotypes a + b are distinct: every X[gc] takes its terms in the order of a)
+        gc = np.sort(np.concatenate([np.broadcast_to(a[i], (len(b), tp)), b], axis=1), axis=1)
+        X[_multiset_ranks(gc)] += gam_p[i] * gam_q
+    return gam_p, gam_q, X
+
+
+def _unit_posterior(llk, H, K, F, f):
+    """float64 [G]: exp(llk + log prior - logsumexp) of a unit under its calling prior (F None: flat); NaN without a finite genotype."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        lj = np.asarray(llk, dtype=np.float64) + _host_log_prior(_genotype_table(H, K), H, K, F, f)
+        norm = _logsumexp(lj)
+        if not np.isfinite(norm):
+            return np.full(len(lj), np.nan), norm
+        return np.where(lj > -np.inf, np.exp(lj - norm), 0.0), norm
+
+
+def cross_posterior(llk, log_x):
+    """(q float64 [G], log Z, mode, its probability): the progeny posterior q = X exp(llk) / Z, the cross evidence log Z, the first
+    maximum of q in VCF order and its probability.  Without a finite term, or with a NaN prior: q NaN, mode -1, probability NaN."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        lj = np.asarray(llk, dtype=np.float64) + np.asarray(log_x, dtype=np.float64)
+        lz = float("nan") if np.any(np.isnan(lj)) else _logsumexp(lj)
+        if not np.isfinite(lz):
+            return np.full(len(lj), np.nan), lz, -1, float("nan")
+        q = np.where(lj > -np.inf, np.exp(lj - lz), 0.0)
+    mode = int(np.argmax(lj))
+    return q, lz, mode, float(np.exp(lj[mode] - lz))
+
+
+def cross_prior_unit(llk_p, K_p, F_p, llk_q, K_q, F_q, H, f, gamete_error=(0.01, 0.01), llk_c=None):
+    """The definition for one trio, in float64: the parents' posteriors under their calling priors (F None: the flat genotype
+    prior; f [H] the record's calling frequencies, None: flat), their gamete tables and the cross prior (cross_prior_tables), and --
+    with the progeny's likelihoods llk_c [G_c] -- its posterior under that prior (cross_posterior).  Returns a dict: gam_p, gam_q,
+    X, log_x, and with llk_c also q, log_z, mode, mode_prob.  A parent without a finite genotype gives NaN throughout."""
+    fr = np.full(H, 1.0 / H) if f is None else np.asarray(f, dtype=np.float64)
+    p_p, _ = _unit_posterior(llk_p, H, K_p, F_p, fr)
+    p_q, _ = _unit_posterior(llk_q, H, K_q, F_q, fr)
+    gam_p, gam_q, X = cross_prior_tables(p_p, K_p, p_q, K_q, H, gamete_error, fr)
+    if np.any(np.isnan(p_p)) or np.any(np.isnan(p_q)):
+        gam_p = np.full(len(gam_p), np.nan) if np.any(np.isnan(p_p)) else gam_p
+        gam_q = np.full(len(gam_q), np.nan) if np.any(np.isnan(p_q)) else gam_q
+        X = np.full(len(X), np.nan)
+    with np.errstate(divide="ignore"):
+        out = dict(gam_p=gam_p, gam_q=gam_q, X=X, log_x=np.log(X))
+    if llk_c is not None:
+        out["q"], out["log_z"], out["mode"], out["mode_prob"] = cross_posterior(llk_c, out["log_x"])
+    return out
+
+
+class Cross:
+    """One cross of a run: the two parents, the progeny (None: every other sample of ploidy t_P + t_Q) and the gamete errors
+    (one value, or one per parent).  resolve() checks it against the samples' ploidies."""
+
+    def __init__(self, parents, progeny=None, gamete_error=0.01):
+        self.parents = tuple(parents)
+        self.progeny = None if progeny is None else list(progeny)
+        e = np.atleast_1d(np.asarray(gamete_error, dtype=np.float64))
+        if len(self.parents) != 2:
+            raise ValueError("cross: two parents are needed")
+        if len(e) not in (1, 2) or not np.all((e >= 0.0) & (e <= 1.0)):
+            raise ValueError("cross: the gamete error is one value, or one per parent, in [0, 1]")
+        self.gamete_error = (float(e[0]), float(e[-1]))
+
+    def resolve(self, samples, ploidy_of):
+        """(P, Q, progeny list, K_c) for the run's samples."""
+        P, Q = self.parents
+        for s in list(self.parents) + list(self.progeny or ()):
+            if s not in samples:
+                raise ValueError("cross: %r is not a sample of this run" % (s,))
+        if P == Q:
+            raise ValueError("cross: the two parents are one sample (%r): a selfing needs the joint over one genotype and is not modelled" % (P,))
+        for s in (P, Q):
+            if int(ploidy_of(s)) < 2 or int(ploidy_of(s)) % 2:
+                raise ValueError("cross: parent %r has ploidy %d: an even ploidy is needed" % (s, int(ploidy_of(s))))
+        Kc = int(ploidy_of(P)) // 2 + int(ploidy_of(Q)) // 2
+        if self.progeny is None:
+            progeny = [s for s in samples if s not in (P, Q) and int(ploidy_of(s)) == Kc]
+        else:
+            progeny = list(self.progeny)
+            for s in progeny:
+                if s in (P, Q):
+                    raise ValueError("cross: %r is a parent and a progeny" % (s,))
+                if int(ploidy_of(s)) != Kc:
+                    raise ValueError("cross: progeny %r has ploidy %d, the cross gives %d" % (s, int(ploidy_of(s)), Kc))
+        return P, Q, progeny, Kc
+
+
+def _cross_evaluable(unit, K):
+    """Whether a unit that needs the kernel takes part: a ploidy and a genotype count within the library's."""
+    return _support_evaluable(unit, K)
+
+
+def _unit_llk(unit, s, K, backend):
+    """The float64 log likelihoods of a sample's reads at a record on `backend`; without reads: zeros."""
+    from math import comb
+
+    sr, locus = unit["reads"][s], unit["locus"]
+    if len(sr["counts"]) == 0:
+        return np.zeros(comb(len(locus.haplotypes) + K - 1, K))
+    return np.asarray(backend.genotype_likelihoods(sr["dists"], K, locus.haplotypes, read_counts=sr["counts"]), dtype=np.float64)
+
+
+def cross_calls_host(units, samples, ploidy_of, inbreeding_of, cross, backend):
+    """The definition of the cross calls over a block, in float64 on `backend` (an object with the reference's
+    genotype_likelihoods; the oracle in the CPU tests): for every called record that needs the kernel and every progeny of `cross`,
+    cross_prior_unit of the parents' and the progeny's likelihoods under their calling priors (inbreeding_of(sample), the record's
+    locus.frequencies).  Returns {(record index, progeny): (genotype tuple, its probability, log Bayes factor of the cross against
+    the calling prior) -- or None where it is not formed: a refused shape, a parent without a finite genotype, no progeny genotype
+    with a finite term}."""
+    P, Q, progeny, Kc = cross.resolve(samples, ploidy_of)
+    KP, KQ = int(ploidy_of(P)), int(ploidy_of(Q))
+    out = {}
+    for ri, unit in enumerate(units):
+        if not unit["needs_kernel"] or unit["invalid"] is not None:
+            continue
+        locus = unit["locus"]
+        H = len(locus.haplotypes)
+        if not all(_cross_evaluable(unit, K) for K in (KP, KQ, Kc)):
+            out.update({(ri, s): None for s in progeny})
+            continue
+        table = None
+        for s in progeny:
+            llk_c = _unit_llk(unit, s, Kc, backend)
+            if table is None:
+                table = cross_prior_unit(_unit_llk(unit, P, KP, backend), KP, inbreeding_of(P), _unit_llk(unit, Q, KQ, backend), KQ,
+                                         inbreeding_of(Q), H, locus.frequencies, cross.gamete_error)
+            q, lz, mode, prob = cross_posterior(llk_c, table["log_x"])
+            _, norm = _unit_posterior(llk_c, H, Kc, inbreeding_of(s), locus.frequencies)
+            if mode < 0 or not np.isfinite(norm):
+                out[(ri, s)] = None
+                continue
+            out[(ri, s)] = (tuple(int(x) for x in _genotype_table(H, Kc)[mode]), prob, lz - norm)
+    return out
+
+
+def _unrank_genotype(index, K):
+    """The ascending alleles of the genotype of VCF index `index` (jitutils.py:279-318)."""
+    from math import comb
+
+    g, rem = [0] * K, int(index)
+    for p in range(K, 0, -1):
+        n = 0
+        while comb(n + p, p) <= rem:
+            n += 1
+        rem -= comb(n + p - 1, p)
+        g[p - 1] = n
+    return tuple(g)
+
+
+def _cross_calls_device(units, samples, ploidy_of, inbreeding_of, cross):
+    """cross_calls_host's result from the device: per shape group one likelihood pass (llks64 alone, cut by the free HBM); the
+    parents' groups first, their gamete tables kept on the device (device.ExactCross), then per progeny group the cross prior of
+    the chunk's records and the posterior launches; the results are read back after everything is enqueued.  A chunk the library
+    refuses is run again unit by unit, and a unit refused on its own -- or one of whose parents was -- has no call (None)."""
+    from .device import ExactCross
+
+    P, Q, progeny, Kc = cross.resolve(samples, ploidy_of)
+    error = dict(zip((P, Q), cross.gamete_error))
+    out, pending = {}, []
+    dev = None
+    groups = _shape_groups(units, ploidy_of)
+
+    def chunks(members, shape, flat, refused):
+        """(chunk, llks64, its records, each unit's record row, its F or None) of a group's members; a refused chunk again unit by
+        unit, a unit refused on its own into `refused`."""
+        todo = [members] if members else []
+        while todo:
+            part = todo.pop(0)
+            for chunk, batch in _estimate_group_batches(units, part, shape, lambda s: 0.0, 8, prior=False):
+                recs = sorted({ri for ri, _ in chunk})
+                row = {ri: i for i, ri in enumerate(recs)}
+                try:
+                    if batch is None:
+                        raise NotImplementedError
+                    yield (chunk, batch.run_llks64(), recs, [row[ri] for ri, _ in chunk],
+                           None if flat else [inbreeding_of(s) for _, s in chunk])
+                except NotImplementedError:
+                    if len(chunk) > 1:
+                        todo.extend([key] for key in chunk)
+                    else:
+                        refused.append(chunk[0])
+
+    for parents_turn in (True, False):
+        for shape, group in groups.items():
+            M, A, H, K = shape
+            who = (P, Q) if parents_turn else progeny
+            group = [key for key in group if units[key[0]]["invalid"] is None and key[1] in who]
+            if not parents_turn:
+                for key in group:
+                    if not _cross_evaluable(units[key[0]], K) or dev is None or any((key[0], s) not in dev.tables for s in (P, Q)):
+                        out[key] = None
+            else:
+                group = [key for key in group if _cross_evaluable(units[key[0]], K)]
+            for flat in (True, False):
+                members = [key for key in group if key not in out and (inbreeding_of(key[1]) is None) == flat]
+                refused = []
+                for chunk, llks, recs, rows, Fs in chunks(members, shape, flat, refused):
+                    if dev is None:
+                        dev = ExactCross()
+                    freqs = np.stack([units[ri]["locus"].frequencies for ri in recs])
+                    try:
+                        if parents_turn:
+                            gam = dev.gametes(llks, H, K, Fs, rows, freqs, [error[s] for _, s in chunk])
+                            for i, key in enumerate(chunk):
+                                dev.tables[key] = gam[i]
+                        else:
+                            log_x = dev.cross_prior(dev.torch.stack([dev.tables[(ri, P)] for ri in recs]),
+                                                    dev.torch.stack([dev.tables[(ri, Q)] for ri in recs]), H, int(ploidy_of(P)), int(ploidy_of(Q)))
+                            pending.append((chunk, dev.posteriors(llks, H, K, log_x, rows, Fs, freqs)))
+                    except NotImplementedError:
+                        # (a shape the cross launches refuse: as the likelihood pass' refusal, unit by unit has the same answer)
+                        refused.extend(chunk)
+                if not parents_turn:
+                    for key in refused:
+                        out[key] = None
+    for chunk, (log_z, mode, prob, log_norm) in pending:
+        lz, md, pr, ln = (t.cpu().numpy() for t in (log_z, mode, prob, log_norm))
+        for i, key in enumerate(chunk):
+            if md[i] < 0 or not np.isfinite(ln[i]):
+                out[key] = None
+            else:
+                out[key] = (_unrank_genotype(md[i], int(ploidy_of(key[1]))), float(pr[i]), float(lz[i] - ln[i]))
+    return out
+
+
+CROSS_FIELDS = (("CGT", "String", "Genotype called under the cross prior of the parents %s and %s"),
+                ("CGPM", "Float", "Posterior probability of CGT under the cross prior"),
+                ("CLBF", "Float", "Natural log Bayes factor of the cross prior against the calling prior"))
+
+
+class CrossCalls:
+    """The writer of `call-exact --cross-calls`: the run's own VCF -- header and record lines as the run writes them -- with three
+    FORMAT fields added to every record: CGT, the genotype of a progeny of the cross under the prior its parents' posteriors imply
+    (cross_prior_unit), CGPM, its posterior probability, and CLBF, the natural log Bayes factor of that prior against the sample's
+    calling prior.  The parents and every sample that is not a progeny carry '.' in all three; so does a progeny in an invalid
+    record (FILTER=LIMIT among them), for a shape the library refuses on the progeny or a parent, where a parent has no finite
+    genotype, and where no progeny genotype has a finite term.  A record with a single haplotype needs no kernel: CGT all 0, CGPM
+    1, CLBF 0.  This is not call-pedigree: the parents are called from their own reads alone and enter as independent plug-in
+    posteriors, there is no double reduction, and a run has one cross.
+
+    samples: the source's; parents: the two sample names; progeny: sample names, or None for every other sample of ploidy
+    t_P + t_Q; gamete_error: one value or one per parent; header_lines: the header of the run's VCF, as a list of lines."""
+
+    def __init__(self, samples, parents, progeny=None, gamete_error=0.01, header_lines=()):
+        self.samples = list(samples)
+        self.cross = Cross(parents, progeny, gamete_error)
+        self.header_lines = list(header_lines)
+        self.lines = []
+
+    def add_block(self, units, lines, ploidy_of, inbreeding_of, backend=None):
+        """The records of a block (what _exact_units returned, after they were called) and their record lines as the main VCF
+        shows them: the lines with the three fields are added.  backend: the definition on that object (cross_calls_host); None =
+        the device.  Returns the calls {(record index, progeny): (genotype, probability, log Bayes factor) or None}."""
+        from .io import vcfstr
+
+        _, _, progeny, Kc = self.cross.resolve(self.samples, ploidy_of)
+        if backend is not None:
+            calls = cross_calls_host(units, self.samples, ploidy_of, inbreeding_of, self.cross, backend)
+        else:
+            calls = _cross_calls_device(units, self.samples, ploidy_of, inbreeding_of, self.cross)
+        for ri, (unit, line) in enumerate(zip(units, lines)):
+            cols = []
+            for s in self.samples:
+                c = calls.get((ri, s))
+                if c is None and s in progeny and unit["invalid"] is None and len(unit["locus"].haplotypes) == 1:
+                    c = ((0,) * Kc, 1.0, 0.0)   # (a single haplotype: one genotype, under either prior)
+                if c is None or s not in progeny or unit["invalid"] is not None:
+                    cols.append(".:.:.")
+                else:
+                    cols.append("%s:%s:%.3f" % ("/".join(str(a) for a in c[0]), vcfstr(c[1]), c[2] + 0.0))
+            f = line.split("\t")
+            f[8] += ":CGT:CGPM:CLBF"
+            f[9:] = ["%s:%s" % (col, add) for col, add in zip(f[9:], cols)]
+            self.lines.append("\t".join(f))
+        return calls
+
+    def header(self):
+        """The run's header with the three declarations after the last ##FORMAT line."""
+        out = list(self.header_lines)
+        at = [i for i, ln in enumerate(out) if ln.startswith("##FORMAT=<")]
+        at = at[-1] + 1 if at else max(len(out) - 1, 0)   # (none declared: before the column line)
+        P, Q = self.cross.parents
+        for k, (name, kind, text) in enumerate(CROSS_FIELDS):
+            out.insert(at + k, '##FORMAT=<ID=%s,Number=1,Type=%s,Description="%s">' % (name, kind, text % (P, Q) if "%s" in text else text))
+        return out
+
+    def text(self):
+        return "\n".join(self.header() + self.lines) + "\n"
+
+    def write(self, path):
+        with open(path, "w") as fh:
+            fh.write(self.text())
+
+
 def _per_sample(value, samples):
     """A scalar, or a {sample: value} mapping (the reference's per-sample ploidy / inbreeding files), as a function."""
     if isinstance(value, dict):
@@ -1249,7 +1610,7 @@ def _blocks(items, n):
 def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.0024, use_base_phred_scores=False,
                prior_frequencies_tag=None, inbreeding=None, calling=None, filter_input_haplotypes=None, read_kw=None,
                records_per_block=4096, shard=None, block_path=None, estimate_frequencies=None, estimate_tolerance=1e-6,
-               estimate_path=None, model_evidence=None, snv_calls=None, allele_depths=None):
+               estimate_path=None, model_evidence=None, snv_calls=None, allele_depths=None, cross_calls=None):
     """`mchap call-exact` over a VCF of known haplotypes: yields one VCF record line per input record (no header).
     sample_bams: ordered mapping sample name -> BAM path (or pool -> [(sample, path)], or a ReadSource); ploidy /
     inbreeding: a value or {sample: value}.  The records are processed in blocks: the (record x sample) units of a block
@@ -1285,7 +1646,11 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
 
     allele_depths: an AlleleDepths over the source's samples; every block's own lines are handed to it after they are formed --
     after the frequency estimate, so the estimated prior is the one used -- and it adds them with ADP, the posterior expected read
-    depth of every allele (the record lines do not depend on it).  Not with `shard`: the file is written by one process."""
+    depth of every allele (the record lines do not depend on it).  Not with `shard`: the file is written by one process.
+
+    cross_calls: a CrossCalls over the source's samples; every block's own lines are handed to it likewise, after the frequency
+    estimate, and it adds them with CGT, CGPM and CLBF: the progeny of its cross called under their parents' cross prior (the
+    record lines do not depend on it).  Not with `shard`."""
     from .vcfheader import report_fields
 
     if model_evidence is not None and shard is not None:
@@ -1294,11 +1659,15 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
         raise ValueError("snv_calls runs as a single process: the SNV file is not gathered from several ranks (shard)")
     if allele_depths is not None and shard is not None:
         raise ValueError("allele_depths runs as a single process: the file is not gathered from several ranks (shard)")
+    if cross_calls is not None and shard is not None:
+        raise ValueError("cross_calls runs as a single process: the file is not gathered from several ranks (shard)")
     source = _source(sample_bams, base_error_rate, use_base_phred_scores, read_kw)
     block_path = _call_block_path(block_path, source)
     samples = source.samples
     if allele_depths is not None and list(allele_depths.samples) != list(samples):
         raise ValueError("allele_depths: its samples are not the source's")
+    if cross_calls is not None and list(cross_calls.samples) != list(samples):
+        raise ValueError("cross_calls: its samples are not the source's")
     if model_evidence is not None and list(model_evidence.samples) != list(samples):
         raise ValueError("model_evidence: its samples are not the source's")
     if snv_calls is not None and list(snv_calls.samples) != list(samples):
@@ -1324,7 +1693,7 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
             alts = unit["locus"].sequences[1:]  # (the input's, minus the alleles --filter-input-haplotypes removed)
             alt = ",".join(alts) if alts else "."
             line = "\t".join([rec["chrom"], str(rec["pos"]), rec["id"], rec["ref"], alt, ".", flt, info, fmt] + [cols[s] for s in samples])
-            if snv_calls is None and allele_depths is None:
+            if snv_calls is None and allele_depths is None and cross_calls is None:
                 yield line
             else:
                 lines.append(line)
@@ -1332,6 +1701,8 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
             snv_calls.add_block(units, lines, ploidy_of, inbreeding_of, calling)
         if allele_depths is not None:
             allele_depths.add_block(units, lines, ploidy_of, inbreeding_of, calling)
+        if cross_calls is not None:
+            cross_calls.add_block(units, lines, ploidy_of, inbreeding_of, calling)
         yield from lines
 
 

@@ -15,6 +15,8 @@ __all__ = [
     "posterior_mode",
     "posterior_mode_batch",
     "allele_read_support",
+    "cross_genotype_prior",
+    "cross_genotype_posteriors",
     "genotype_likelihoods",
     "genotype_posteriors",
     "posterior_allele_frequencies",
@@ -231,6 +233,43 @@ def allele_read_support(reads, ploidy, haplotypes, read_counts=None, prior=None,
     if per_read:
         return got[0].cpu().numpy()[0], got[1].cpu().numpy()[0]
     return got.cpu().numpy()[0]
+
+
+def cross_genotype_prior(parent_posteriors_p, ploidy_p, parent_posteriors_q, ploidy_q, n_alleles, gamete_error=(0, 0), frequencies=None):
+    """The distribution X float64 [G_c] of the cross of two parents over the genotypes of ploidy ploidy_p / 2 + ploidy_q / 2 (not
+    a reference function; the definition: application.cross_prior_tables): parent_posteriors_p / _q the parents' genotype
+    posteriors [G_p] / [G_q] in VCF order, even ploidies, n_alleles haplotypes; gamete_error (e_p, e_q) mixes the multinomial of
+    `frequencies` [n_alleles] (None: flat) into either gamete table.  No double reduction; the parents are independent."""
+    import torch
+
+    from .device import ExactCross
+
+    H = int(n_alleles)
+    fr = np.full((1, H), 1.0 / H) if frequencies is None else np.asarray(frequencies, dtype=np.float64).reshape(1, H)
+    dev = ExactCross()
+    gam = []
+    for p, K, e in ((parent_posteriors_p, ploidy_p, gamete_error[0]), (parent_posteriors_q, ploidy_q, gamete_error[1])):
+        with np.errstate(divide="ignore"):
+            # (the posterior itself as the likelihood under the flat genotype prior: the kernel's p is the given one again)
+            llk = torch.from_numpy(np.log(np.ascontiguousarray(p, dtype=np.float64))).to(dev.device)
+        gam.append(dev.gametes(llk, H, int(K), None, [0], fr, [float(e)]))
+    log_x = dev.cross_prior(gam[0], gam[1], H, int(ploidy_p), int(ploidy_q))
+    return torch.exp(log_x)[0].cpu().numpy()
+
+
+def cross_genotype_posteriors(llks, log_cross_prior):
+    """The posterior float64 [G_c] of a progeny with log likelihoods llks [G_c] under the log cross prior [G_c]
+    (log of cross_genotype_prior): exp(llks + log_cross_prior - log Z).  NaN where no genotype has a finite term."""
+    import torch
+
+    from .device import ExactCross
+
+    dev = ExactCross()
+    llk = torch.from_numpy(np.ascontiguousarray(llks, dtype=np.float64)).to(dev.device)
+    lx = torch.from_numpy(np.ascontiguousarray(log_cross_prior, dtype=np.float64).reshape(1, -1)).to(dev.device)
+    G = int(llk.numel())
+    # (the shape is given by the arrays alone: any (H, K) with C(H + K - 1, K) = G streams them alike -- K = 1 over G alleles)
+    return dev.posteriors(llk, G, 1, lx, [0], full=True)[4][0].cpu().numpy()
 
 
 def call_arrays_batch(reads, ploidy, haplotypes, read_counts=None, prior=None, return_arrays=True):

@@ -16,7 +16,8 @@ also writes a table of every sample's log evidence under candidate (ploidy, inbr
 the VCF, header included, as it is without those flags; so does `call-exact --snv-calls FILE [--snv-report GP]`, which writes the
 SNV-level VCF `atomize` would make of the run's output with GQ, DS and ACP from the exact SNV genotype posteriors
 (application.SnvCalls), and `call-exact --allele-depths FILE`, which writes the run's VCF again with ADP, the posterior expected read
-depth of every allele (application.AlleleDepths).  `atomize --haplotypes FILE` is host only (mchap_amd/atomize.py)."""
+depth of every allele (application.AlleleDepths), and `call-exact --cross-calls FILE --cross-parents P Q`, which writes the run's VCF
+again with the progeny of that cross called under their parents' cross prior (application.CrossCalls).  `atomize --haplotypes FILE` is host only (mchap_amd/atomize.py)."""
 import argparse
 import sys
 
@@ -165,6 +166,18 @@ def build_parser(program):
                            help="(not a reference flag) write to FILE, when the run ends, this run's VCF with one field added: ADP, the "
                                 "posterior expected read depth of every allele (FORMAT per sample, INFO their sum; Number=R, so FILE "
                                 "serves as --haplotypes with --filter-input-haplotypes \"ADP>=1\")")
+            p.add_argument("--cross-calls", type=str, nargs=1, default=[None], metavar="FILE",
+                           help="(not a reference flag) write to FILE, when the run ends, this run's VCF with three FORMAT fields added "
+                                "for the progeny of the cross --cross-parents: CGT, the genotype under the prior the parents' posteriors "
+                                "imply, CGPM, its probability, and CLBF, the log Bayes factor of that prior against the calling prior")
+            p.add_argument("--cross-parents", type=str, nargs=2, default=None, metavar=("P", "Q"),
+                           help="(not a reference flag) with --cross-calls: the two parents of the cross, by sample name")
+            p.add_argument("--cross-progeny", type=str, nargs="+", default=None, metavar="SAMPLE",
+                           help="(not a reference flag) with --cross-calls: the progeny of the cross (default: every other sample whose "
+                                "ploidy is half of P's plus half of Q's)")
+            p.add_argument("--gamete-error", type=float, nargs="+", default=None, metavar="E",
+                           help="(not a reference flag) with --cross-calls: the probability that a gamete is drawn from the population "
+                                "and not from its parent, one value or one for P and one for Q, in [0, 1] (default: 0.01)")
             p.add_argument("--snv-report", type=str, nargs="+", default=None, metavar="FIELD", choices=["GP"],
                            help="(not a reference flag) with --snv-calls: GP adds the SNV genotype posteriors as a sixth FORMAT field")
     p.add_argument("--report", type=str, nargs="*", default=[],
@@ -231,7 +244,7 @@ def run(argv, out=None):
                                     read_group_field=id_field, mapping_quality=args.mapping_quality[0],
                                     skip_duplicates=args.skip_duplicates, skip_qcfail=args.skip_qcfail,
                                     skip_supplementary=args.skip_supplementary, workers=args.cores[0])
-    seed = evidence = snv_calls = allele_depths = header = None
+    seed = evidence = snv_calls = allele_depths = cross_calls = header = None
     block_path = BLOCK_PATHS[args.block_path]
     if program == "assemble":
         if args.targets[0] is not None and args.region[0] is not None:
@@ -270,15 +283,17 @@ def run(argv, out=None):
                                  "frequencies to estimate")
             evidence = model_evidence_settings(args, samples, inbreeding, tag, estimate, world)
             snv_calls = snv_calls_settings(args, samples, world, ["mchap_amd"] + header_argv)
-            if args.allele_depths[0] is not None:
+            if args.allele_depths[0] is not None or args.cross_calls[0] is not None:
                 header = vcfheader.header_lines(program, ["mchap_amd"] + header_argv, samples, contigs, report=report, random_seed=seed,
                                                 estimate=estimate is not None)
             allele_depths = allele_depths_settings(args, samples, world, header)
+            cross_calls = cross_calls_settings(args, samples, ploidy, world, header)
             records = application.call_exact(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
                                              inbreeding=inbreeding, filter_input_haplotypes=args.filter_input_haplotypes[0], shard=shard,
                                              block_path=block_path, estimate_frequencies=estimate,
                                              estimate_tolerance=1e-6 if args.estimate_tolerance[0] is None else args.estimate_tolerance[0],
-                                             model_evidence=evidence, snv_calls=snv_calls, allele_depths=allele_depths)
+                                             model_evidence=evidence, snv_calls=snv_calls, allele_depths=allele_depths,
+                                             cross_calls=cross_calls)
         else:
             seed = args.mcmc_seed[0]
             records = application.call(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
@@ -295,7 +310,7 @@ def run(argv, out=None):
         if rank != 0:
             return n_mine
         lines = [ln for part in gathered for ln in part]
-    if header is None:   # (--allele-depths has formed it already: its file carries the very same lines)
+    if header is None:   # (--allele-depths and --cross-calls have formed it already: their files carry the very same lines)
         header = vcfheader.header_lines(program, ["mchap_amd"] + header_argv, samples, contigs, report=report, random_seed=seed,
                                         estimate=program == "call-exact" and args.estimate_prior_frequencies[0] is not None)
     for line in header:
@@ -313,6 +328,8 @@ def run(argv, out=None):
         snv_calls.write(args.snv_calls[0])
     if allele_depths is not None:
         allele_depths.write(args.allele_depths[0])
+    if cross_calls is not None:
+        cross_calls.write(args.cross_calls[0])
     return n
 
 
@@ -321,10 +338,12 @@ EVIDENCE_FLAGS = ("--model-evidence", "--evidence-ploidy", "--evidence-inbreedin
 SNV_FLAGS = ("--snv-calls", "--snv-report")
 # ... and the flag of the allele-depths file
 ALLELE_DEPTH_FLAGS = ("--allele-depths",)
+# ... and the flags of the cross-calls file
+CROSS_FLAGS = ("--cross-calls", "--cross-parents", "--cross-progeny", "--gamete-error")
 
 
 def _header_argv(argv, options):
-    """The command line as the VCF header states it: without the model-evidence, SNV-file and allele-depths flags and their values -- the VCF, header included,
+    """The command line as the VCF header states it: without the model-evidence, SNV-file, allele-depths and cross-calls flags and their values -- the VCF, header included,
     is byte for byte what the run writes without them.  options: the parser's option strings; a flag is resolved as argparse
     resolves it (the exact name, else the one option it is a prefix of), so an abbreviated flag is taken out too."""
     out, skipping = [], False
@@ -332,7 +351,7 @@ def _header_argv(argv, options):
         if a.startswith("--"):
             name = a.split("=", 1)[0]
             full = [name] if name in options else [o for o in options if o.startswith(name)]
-            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS + SNV_FLAGS + ALLELE_DEPTH_FLAGS
+            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS + SNV_FLAGS + ALLELE_DEPTH_FLAGS + CROSS_FLAGS
         if not skipping:
             out.append(a)
     return out
@@ -384,6 +403,30 @@ def allele_depths_settings(args, samples, world, header_lines):
     if world > 1:
         raise ValueError("--allele-depths runs as a single process: the file is not gathered from several ranks (WORLD_SIZE > 1)")
     return application.AlleleDepths(samples, header_lines)
+
+
+def cross_calls_settings(args, samples, ploidy, world, header_lines):
+    """The --cross-calls / --cross-parents / --cross-progeny / --gamete-error flags of call-exact -> an application.CrossCalls over
+    the run's header lines, or None without --cross-calls (any of the other three is then an error).  The cross is checked here,
+    before any work: the sample names, two different parents of even ploidy, progeny of ploidy t_P + t_Q."""
+    from . import application
+
+    if args.cross_calls[0] is None:
+        for flag, value in (("--cross-parents", args.cross_parents), ("--cross-progeny", args.cross_progeny),
+                            ("--gamete-error", args.gamete_error)):
+            if value is not None:
+                raise ValueError("%s needs --cross-calls" % flag)
+        return None
+    if args.cross_parents is None:
+        raise ValueError("--cross-calls needs --cross-parents P Q")
+    if world > 1:
+        raise ValueError("--cross-calls runs as a single process: the file is not gathered from several ranks (WORLD_SIZE > 1)")
+    error = [0.01] if args.gamete_error is None else list(args.gamete_error)
+    if len(error) > 2 or not all(0.0 <= e <= 1.0 for e in error):   # (False for NaN too)
+        raise ValueError("--gamete-error: one value, or one for each parent, in [0, 1]")
+    calls = application.CrossCalls(samples, args.cross_parents, args.cross_progeny, error, header_lines)
+    calls.cross.resolve(list(samples), application._per_sample(ploidy, samples))
+    return calls
 
 
 def _run_atomize(argv, args, out):

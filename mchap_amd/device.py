@@ -856,6 +856,140 @@ class ExactReadSupport:
         return (depth, post) if per_read else depth
 
 
+class ExactCross:
+    """Progeny calls under their parents' cross prior for exact-caller units whose likelihoods are resident on the device
+    (mchap_exact_gametes_device, mchap_exact_cross_prior_device, mchap_exact_cross_posterior_device): the parents' gamete tables, the
+    cross prior of a record, the progeny's posterior under it.  `tables` keeps what the caller puts there -- the gamete rows of a
+    block's records between the parents' groups and the progeny's -- on the device."""
+
+    def __init__(self, device=None):
+        self.torch = _torch()
+        self.device = _device(self.torch, device)
+        self.launches = 0      # calls enqueued
+        self.log_norm = None   # the parents' normalisers [U] of the last gametes call, on the device
+        self.tables = {}
+
+    _tensor = ExactModelEvidence._tensor
+
+    @staticmethod
+    def _shape(H, K):
+        if K < 1 or K > _lib.MAX_PLOIDY_GENERAL or comb(H + K - 1, K) >= 1 << 62:
+            raise NotImplementedError("mchap_hip: ploidy %d over %d haplotypes is beyond this build's exact caller" % (K, H))
+        return comb(H + K - 1, K)
+
+    def _prior(self, U, H, inbreeding, unit_row, freqs):
+        """(d_F or None, d_row, d_fr, stride) of a group: F checked on the host copy, the rows against the table."""
+        torch, dev = self.torch, self.device
+        d_F = None
+        if inbreeding is not None:
+            F = np.array(np.broadcast_to(np.asarray(inbreeding, dtype=np.float64), (U,)))
+            if not np.all((F >= 0.0) & (F < 1.0)):   # (False for NaN and infinities too)
+                raise ValueError("inbreeding: every F must lie in [0, 1)")
+            d_F = torch.from_numpy(F).to(dev)
+        rows = np.ascontiguousarray(unit_row, dtype=np.int32)
+        d_fr = self._tensor(freqs, torch.float64, np.float64)
+        assert d_fr.dim() == 2 and int(d_fr.shape[1]) >= H
+        assert rows.shape == (U,) and (U == 0 or (int(rows.min()) >= 0 and int(rows.max()) < int(d_fr.shape[0])))
+        return d_F, torch.from_numpy(rows).to(dev), d_fr, int(d_fr.shape[1])
+
+    def _workspace(self, wsb, extra, what):
+        free, _ = self.torch.cuda.mem_get_info()
+        if wsb < 0 or wsb + extra > free:
+            raise NotImplementedError("mchap_hip: %s: the shape is refused, or its workspace does not fit the device" % what)
+        return self.torch.empty(max(wsb, 16), dtype=self.torch.uint8, device=self.device)
+
+    def gametes(self, llks64, n_haps, ploidy, inbreeding, unit_row, freqs, gamete_error):
+        """The gamete tables of parent units of one shape (n_haps, even ploidy), enqueued on torch's current stream: llks64 a
+        float64 tensor [U * G] on the device; inbreeding [U] (or a scalar), every F in [0, 1), or None: the flat genotype prior;
+        unit_row [U]: each unit's row of freqs [rows, stride >= n_haps] -- read under the flat prior too, for the gamete error's
+        multinomial --; gamete_error [U] (or a scalar), every e in [0, 1].  F and e are checked here, on the host copies.  Returns
+        the float64 tensor [U, C(H + t - 1, t)] on the device, NaN rows for a unit without a finite genotype.  A shape the library
+        refuses: NotImplementedError."""
+        torch, dev = self.torch, self.device
+        H, K = int(n_haps), int(ploidy)
+        G = self._shape(H, K)
+        if K % 2:
+            raise ValueError("gametes: a parent of odd ploidy %d" % K)
+        assert llks64.dtype == torch.float64 and llks64.is_contiguous() and llks64.numel() % G == 0
+        U = llks64.numel() // G
+        e = np.array(np.broadcast_to(np.asarray(gamete_error, dtype=np.float64), (U,)))
+        if not np.all((e >= 0.0) & (e <= 1.0)):
+            raise ValueError("gamete_error: every e must lie in [0, 1]")
+        d_F, d_row, d_fr, stride = self._prior(U, H, inbreeding, unit_row, freqs)
+        NA = comb(H + K // 2 - 1, K // 2)
+        out = torch.empty((U, NA), dtype=torch.float64, device=dev)
+        self.log_norm = torch.empty(U, dtype=torch.float64, device=dev)
+        if U == 0:
+            return out
+        L = _lib.lib()
+        wsb = int(L.mchap_exact_gametes_workspace_bytes(U, H, K))
+        ws = self._workspace(wsb, 0, "gametes of %d units of ploidy %d over %d haplotypes" % (U, K, H))
+        d_e = torch.from_numpy(e).to(dev)
+        _lib.check(L.mchap_exact_gametes_device(
+            U, _ptr(llks64), H, K, _ptr(d_F), _ptr(d_row), _ptr(d_fr), stride, _ptr(d_e), _ptr(out), _ptr(self.log_norm), _ptr(ws),
+            C.c_int64(wsb), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        self.launches += 1
+        return out
+
+    def cross_prior(self, gametes_p, gametes_q, n_haps, ploidy_p, ploidy_q):
+        """log X [rows, G_c] on the device from the two parents' gamete tables [rows, .] (float64 tensors on the device, a row per
+        record): exactly -inf where every product is 0."""
+        torch, dev = self.torch, self.device
+        H, KP, KQ = int(n_haps), int(ploidy_p), int(ploidy_q)
+        if KP < 2 or KQ < 2 or KP % 2 or KQ % 2:
+            raise ValueError("cross_prior: parents of even ploidy are needed, got %d and %d" % (KP, KQ))
+        self._shape(H, KP), self._shape(H, KQ)
+        GC = self._shape(H, KP // 2 + KQ // 2)
+        rows = int(gametes_p.shape[0])
+        for t, K in ((gametes_p, KP), (gametes_q, KQ)):
+            assert t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, comb(H + K // 2 - 1, K // 2))
+        free, _ = torch.cuda.mem_get_info()
+        if rows * GC * 8 > free:
+            raise NotImplementedError("mchap_hip: the cross prior of %d records over %d genotypes does not fit the device" % (rows, GC))
+        out = torch.empty((rows, GC), dtype=torch.float64, device=dev)
+        if rows:
+            _lib.check(_lib.lib().mchap_exact_cross_prior_device(rows, _ptr(gametes_p), _ptr(gametes_q), H, KP, KQ, _ptr(out),
+                                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            self.launches += 1
+        return out
+
+    def posteriors(self, llks64, n_haps, ploidy, log_cross, unit_row, inbreeding=None, freqs=None, full=False):
+        """The progeny units of one shape under the cross prior: llks64 [U * G_c] and log_cross [rows, G_c] float64 tensors on the
+        device, unit_row [U] each unit's row of log_cross -- and of freqs [rows, stride >= n_haps], the calling prior's
+        frequencies (inbreeding [U], a scalar, or None: the flat genotype prior).  Returns float64 / int64 tensors on the device:
+        (log_z [U], mode [U], mode_prob [U], log_norm [U]) -- the cross evidence, the first maximum in VCF order (-1: none), its
+        probability, the unit's evidence under its calling prior -- and with full=True a fifth, the posterior [U, G_c]."""
+        torch, dev = self.torch, self.device
+        H, K = int(n_haps), int(ploidy)
+        G = self._shape(H, K)
+        assert llks64.dtype == torch.float64 and llks64.is_contiguous() and llks64.numel() % G == 0
+        assert log_cross.dtype == torch.float64 and log_cross.is_contiguous() and log_cross.dim() == 2 and int(log_cross.shape[1]) == G
+        U = llks64.numel() // G
+        rows = np.ascontiguousarray(unit_row, dtype=np.int32)
+        assert rows.shape == (U,) and (U == 0 or (int(rows.min()) >= 0 and int(rows.max()) < int(log_cross.shape[0])))
+        d_F = d_fr = None
+        stride = 0
+        d_row = torch.from_numpy(rows).to(dev)
+        if inbreeding is not None:
+            d_F, _, d_fr, stride = self._prior(U, H, inbreeding, unit_row, freqs)
+        log_z, prob, norm = (torch.empty(U, dtype=torch.float64, device=dev) for _ in range(3))
+        mode = torch.empty(U, dtype=torch.int64, device=dev)
+        post = None
+        if U:
+            L = _lib.lib()
+            wsb = int(L.mchap_exact_cross_posterior_workspace_bytes(U, H, K))
+            ws = self._workspace(wsb, U * G * 8 if full else 0, "cross posterior of %d units of ploidy %d over %d haplotypes" % (U, K, H))
+            post = torch.empty((U, G), dtype=torch.float64, device=dev) if full else None
+            _lib.check(L.mchap_exact_cross_posterior_device(
+                U, _ptr(llks64), H, K, _ptr(log_cross), _ptr(d_row), _ptr(d_F), _ptr(d_row), _ptr(d_fr), stride, _ptr(log_z),
+                _ptr(mode), _ptr(prob), _ptr(norm), _ptr(post), _ptr(ws), C.c_int64(wsb),
+                C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            self.launches += 1
+        elif full:
+            post = torch.empty((0, G), dtype=torch.float64, device=dev)
+        return (log_z, mode, prob, norm, post) if full else (log_z, mode, prob, norm)
+
+
 class DenovoRaggedBatch(_OwnBuffers):
     """Units of different shapes (loci with different numbers of SNVs and alleles, samples with different read depths,
     per-sample ploidy / inbreeding) in ONE sampler launch, with the posterior summary and the replicate incongruence
