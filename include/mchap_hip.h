@@ -479,6 +479,42 @@ int mchap_exact_cross_posterior_device(int n_units, const double *llks64, int n_
                                        double *log_norm, double *posteriors, void *workspace, int64_t workspace_bytes,
                                        void *stream);
 
+/* The parents and the progeny of one cross called jointly (call-exact --family-calls): the exact joint posterior of one nuclear
+ * family per record.  n_records records of one shape -- n_haps haplotypes, parents P and Q of even ploidies, gametes of
+ * t = ploidy / 2 haplotypes, n_progeny progeny of ploidy t_P + t_Q each; multisets in VCF order -- in one call:
+ *   gamma_u(a | g) = (1 - e_u) prod_h C(c_h(g), a_h) / C(K_u, t_u) + e_u Mult(a; t_u, f),
+ *   M_c[gP][gQ]    = sum_a sum_b gamma_P(a | gP) gamma_Q(b | gQ) exp(llk_c[rank(a + b)] - m_c),        m_c = max llk_c,
+ *   w[gP][gQ]      = exp(lp_P[gP] + llk_P[gP] + lp_Q[gQ] + llk_Q[gQ] + sum_c (log M_c + m_c) - log_z_fam),
+ *   post_p = sum_gQ w,  post_q = sum_gP w,
+ *   q[c][gc]       = exp(llk_c[gc] - m_c) sum_{a in gc} (gamma_P^T (w / M_c) gamma_Q)[a][gc - a],
+ *   pred_log_evidence[c] = m_c - log sum (w / M_c)     = log Z_fam - log Z_fam(without c).
+ * lp_u is the log of the parent's calling prior: the flat genotype prior (inbreeding_u = NULL) or the Dirichlet-multinomial at
+ * inbreeding_u[r] and row r of `frequencies` [n_records][stride]; that row is f of Mult too, always read.  gamete_error_u [n_records].
+ * llks_p [R][G_P], llks_q [R][G_Q], llks_c [R][n_progeny][G_c]; progeny_reads int32 [R][n_progeny] (NULL: all 1): a progeny with
+ * 0 has no reads -- its likelihoods are not read, it adds exactly nothing to the sum over c, its q is formed with w itself and its
+ * pred_log_evidence is 0.  An entry of exp(llk_c - m_c) that underflows is 0; w / M_c is 0 where w is 0.  n_progeny = 0: post_p,
+ * post_q are the parents' own calling posteriors.
+ * Out: post_p [R][G_P], post_q [R][G_Q], their first maxima in VCF order mode_p, mode_q [R] and those probabilities; per progeny
+ * q [R][n][G_c] (may be NULL), mode_c, mode_prob_c, pred_log_evidence [R][n]; log_z_fam [R].  A record whose log_z_fam is not
+ * finite -- a parent or a progeny with reads that has no finite genotype, or Z_fam = 0, which needs a gamete error of 0 or a zero
+ * frequency -- is null: log_z_fam NaN or -inf, every mode -1, every other output NaN; its neighbours are untouched.
+ * Every stage is gather-form: one owning lane per output cell, a fixed summation order (sub-multisets in VCF order of a, then of
+ * b; rows in row order), no atomics; equal inputs give equal bits whatever the place of a record in the call.  The one
+ * [G_P][G_Q] array per record (the sum over c, then w) lives in `workspace`: mchap_exact_family_workspace_bytes (-1: a ploidy
+ * outside 1..MCHAP_MAX_PLOIDY_DENOVO, an odd parent, 2^31 parent genotypes or more); a workspace smaller than that is
+ * MCHAP_ERR_LIMIT -- nothing is allocated behind the caller's back.  A row of M_c and of w / M_c is kept in LDS where it fits 64 KB
+ * and in the workspace otherwise (a second [G_P][G_Q] array); force_fallback != 0 takes the second path at any size (the workspace
+ * is then the larger one).  Every F must lie in [0, 1) and every e in [0, 1]: the caller's duty (device.ExactFamily checks its host
+ * copies).  Enqueue on `stream`, no synchronisation. */
+int64_t mchap_exact_family_workspace_bytes(int n_records, int n_haps, int ploidy_p, int ploidy_q, int force_fallback);
+int mchap_exact_family_device(int n_records, int n_progeny, const double *llks_p, const double *llks_q, const double *llks_c,
+                              const int32_t *progeny_reads, int n_haps, int ploidy_p, int ploidy_q, const double *inbreeding_p,
+                              const double *inbreeding_q, const double *frequencies, int stride, const double *gamete_error_p,
+                              const double *gamete_error_q, double *post_p, int64_t *mode_p, double *mode_prob_p, double *post_q,
+                              int64_t *mode_q, double *mode_prob_q, double *q, int64_t *mode_c, double *mode_prob_c,
+                              double *pred_log_evidence, double *log_z_fam, void *workspace, int64_t workspace_bytes,
+                              int force_fallback, void *stream);
+
 /* Summaries of given posterior arrays [U][G] (calling.exact.posterior_allele_frequencies 332-369, the sum of
  * alternate_dosage_posteriors 372-407 for the array's mode): device pointers, any output may be NULL. */
 int mchap_exact_posterior_summaries_batch_device(int n_units, const double *posteriors, int64_t n_genotypes, int ploidy,

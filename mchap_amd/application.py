@@ -1536,6 +1536,365 @@ class CrossCalls:
             fh.write(self.text())
 
 
+# ---------------------------------------------------------------------------------------------------------
+# call-exact --family-calls: the parents and the progeny of one cross called jointly (the exact joint of one nuclear family)
+# ---------------------------------------------------------------------------------------------------------
+def gamete_rows(H, K, f, error):
+    """float64 [G, C(H + t - 1, t)], t = K / 2: gamma(a | g), the gamete distribution of every single genotype g of even ploidy K,
+        gamma(a | g) = (1 - error) prod_h C(c_h(g), a_h) / C(K, t) + error Mult(a; t, f)
+    -- gamete_table of a one-hot posterior at g, for every g at once: a sparse row (the sub-multisets of g) plus a rank-one row."""
+    from math import comb, factorial
+
+    if K < 2 or K % 2:
+        raise ValueError("a parent of ploidy %d: the gametes of an even ploidy alone are formed" % K)
+    t = K // 2
+    f = np.asarray(f, dtype=np.float64)
+    a = _genotype_table(H, t)
+    dg, da = _dosages(_genotype_table(H, K), H), _dosages(a, H)
+    binom = np.array([[comb(n, k) for k in range(K + 1)] for n in range(K + 1)], dtype=np.float64)
+    own = np.prod(binom[dg[:, None, :], da[None, :, :]], axis=2) / comb(K, t)
+    coef = np.array([factorial(t) // int(np.prod([factorial(int(x)) for x in row])) for row in da], dtype=np.float64)
+    pf = np.ones(len(a))
+    for i in range(t):
+        pf = pf * f[a[:, i]]
+    return (1.0 - error) * own + error * (coef * pf)[None, :]
+
+
+def gamete_pair_ranks(H, tp, tq):
+    """int64 [NA_P, NA_Q]: the VCF index of the genotype a + b for every pair of gametes of tp and tq haplotypes."""
+    a, b = _genotype_table(H, tp), _genotype_table(H, tq)
+    g = np.sort(np.concatenate([np.repeat(a, len(b), axis=0), np.tile(b, (len(a), 1))], axis=1), axis=1)
+    return _multiset_ranks(g).reshape(len(a), len(b))
+
+
+def _matmul(a, b):
+    """a @ b; small operands through einsum's own loops -- a threaded BLAS spends far longer waking its threads than multiplying
+    matrices of a few dozen rows, and family_unit forms several per progeny."""
+    if a.shape[0] * a.shape[1] * b.shape[1] < 1 << 21:
+        return np.einsum("ij,jk->ik", a, b)
+    return a @ b
+
+
+def family_unit(llk_p, K_p, F_p, llk_q, K_q, F_q, H, f, gamete_error=(0.01, 0.01), llk_progeny=()):
+    """The definition of the joint call of one nuclear family at one record, in float64, in the factorised form the kernels take
+    (exact_family_kernel.hpp).  Parents P, Q of even ploidies with log likelihoods llk_p [G_P], llk_q [G_Q] and calling priors lp
+    (F None: the flat genotype prior; f [H] the record's calling frequencies, None: flat); progeny c of ploidy K_p / 2 + K_q / 2
+    with log likelihoods llk_progeny[c] [G_c], or None for a progeny without reads.  With gamma = gamete_rows and
+    T_c[a][b] = exp(llk_c[rank(a + b)] - m_c), m_c = max llk_c:
+        M_c[gP][gQ] = sum_a sum_b gamma_P(a | gP) gamma_Q(b | gQ) T_c[a][b]                  (the progeny's factor, over e^{m_c})
+        J[gP][gQ]   = exp(lp_P + llk_P + lp_Q + llk_Q + sum_c (log M_c + m_c)),  Z = sum J,  w = J / Z
+        post_p = sum_gQ w, post_q = sum_gP w
+        q_c[gc] = exp(llk_c[gc] - m_c) sum_{a in gc} R_c[a][gc - a],  R_c = gamma_P^T (w / M_c) gamma_Q
+        pred_c  = m_c - log sum (w / M_c) = log Z - log Z(without c)                         the predictive log evidence of c
+    Edges: a progeny without reads adds exactly 0 to the exponent and is left out of the product; its q_c is formed with w itself
+    and its pred_c is 0.  Without progeny post_p, post_q are the parents' own calling posteriors.  An entry of T_c more than about
+    745 nats below the progeny's best underflows to 0; w / M_c is 0 where w is 0.  A parent or a progeny (with reads) without a
+    finite genotype, or Z = 0 (possible with a gamete error of 0 or zero frequencies alone), makes every field null: NaN arrays, NaN
+    log_z, modes -1.  Modes are the first maximum in VCF order.
+    Returns a dict: post_p, post_q, q (list of [G_c]), log_z, pred [n], mode_p, mode_q, prob_p, prob_q, modes [n], probs [n]."""
+    from math import comb
+
+    fr = np.full(H, 1.0 / H) if f is None else np.asarray(f, dtype=np.float64)
+    tp, tq = K_p // 2, K_q // 2
+    gam_p = gamete_rows(H, K_p, fr, float(gamete_error[0]))
+    gam_q = gamete_rows(H, K_q, fr, float(gamete_error[1]))
+    rank = gamete_pair_ranks(H, tp, tq)
+    GC = comb(H + tp + tq - 1, tp + tq)
+    n = len(llk_progeny)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        a_p = np.asarray(llk_p, dtype=np.float64) + _host_log_prior(_genotype_table(H, K_p), H, K_p, F_p, fr)
+        a_q = np.asarray(llk_q, dtype=np.float64) + _host_log_prior(_genotype_table(H, K_q), H, K_q, F_q, fr)
+        S = np.zeros((len(a_p), len(a_q)))
+        factors = []
+        for llk in llk_progeny:
+            if llk is None:
+                factors.append(None)
+                continue
+            llk = np.asarray(llk, dtype=np.float64)
+            m = float(np.max(llk))
+            M = _matmul(_matmul(gam_p, np.exp(llk[rank] - m)), gam_q.T)
+            S += np.log(M) + m
+            factors.append((llk, m))
+        L = S + a_p[:, None] + a_q[None, :]
+        lz = float("nan") if np.any(np.isnan(L)) else _logsumexp(L)
+        if not np.isfinite(lz):
+            nan = float("nan")
+            return dict(post_p=np.full(len(a_p), nan), post_q=np.full(len(a_q), nan), q=[np.full(GC, nan) for _ in range(n)],
+                        log_z=nan, pred=np.full(n, nan), mode_p=-1, mode_q=-1, prob_p=nan, prob_q=nan,
+                        modes=np.full(n, -1, dtype=np.int64), probs=np.full(n, nan))
+        w = np.where(L > -np.inf, np.exp(L - lz), 0.0)
+        post_p, post_q = w.sum(axis=1), w.sum(axis=0)
+        q, pred = [], np.zeros(n)
+        for c, fac in enumerate(factors):
+            if fac is None:
+                d, scale = w, np.ones(GC)
+            else:
+                llk, m = fac
+                M = _matmul(_matmul(gam_p, np.exp(llk[rank] - m)), gam_q.T)
+                d = np.where(w == 0.0, 0.0, w / M)
+                scale = np.exp(llk - m)
+                pred[c] = m - np.log(d.sum())
+            R = _matmul(_matmul(gam_p.T, d), gam_q)
+            q.append(scale * np.bincount(rank.ravel(), weights=R.ravel(), minlength=GC))
+    mode_p, mode_q = int(np.argmax(post_p)), int(np.argmax(post_q))
+    modes = np.array([int(np.argmax(x)) for x in q], dtype=np.int64)
+    return dict(post_p=post_p, post_q=post_q, q=q, log_z=lz, pred=pred, mode_p=mode_p, mode_q=mode_q, prob_p=float(post_p[mode_p]),
+                prob_q=float(post_q[mode_q]), modes=modes, probs=np.array([float(x[k]) for x, k in zip(q, modes)]))
+
+
+def _family_record_bytes(H, KP, KQ):
+    """The device bytes the family launches need for one record (its [G_P][G_Q] array and the smaller stages), or -1 for a shape
+    they refuse: sums of products of genotype counts, the carve of mchap_exact_family_workspace_bytes restated on the host so that
+    the definition on a backend sizes a record as the device path does."""
+    from math import comb
+
+    from ._lib import MAX_PLOIDY_GENERAL
+
+    if not all(2 <= K <= MAX_PLOIDY_GENERAL and K % 2 == 0 for K in (KP, KQ)):
+        return -1
+    GP, GQ = comb(H + KP - 1, KP), comb(H + KQ - 1, KQ)
+    NAP, NAQ = comb(H + KP // 2 - 1, KP // 2), comb(H + KQ // 2 - 1, KQ // 2)
+    if GP >= 1 << 31 or GQ >= 1 << 31:
+        return -1
+    staged = (NAQ + GQ) * 8 <= 64 * 1024
+    return GP * GQ * 8 * (1 if staged else 2) + (2 * GP * NAQ + 2 * NAP * NAQ + 3 * GP + GQ) * 8
+
+
+def _family_result(H, KP, KQ, Kc, P, Q, progeny, reads, mode_p, prob_p, mode_q, prob_q, modes, probs, pred, log_z, norms):
+    """A record's family calls from the definition's or the device's numbers: None for a null record, else (INFO FLBF, {sample:
+    (genotype, its probability, FLBF or None)}).  norms {sample: the log evidence of the sample's reads under its own calling
+    prior}; reads {progeny: whether it has reads} -- a progeny without reads has FLBF 0 and no part in the INFO value."""
+    if mode_p < 0 or mode_q < 0 or not np.isfinite(log_z) or not all(np.isfinite(norms[s]) for s in (P, Q)):
+        return None
+    calls = {P: (_unrank_genotype(mode_p, KP), float(prob_p), None), Q: (_unrank_genotype(mode_q, KQ), float(prob_q), None)}
+    alone = norms[P] + norms[Q]
+    for c, s in enumerate(progeny):
+        if modes[c] < 0 or (reads[s] and not np.isfinite(norms[s])):
+            return None
+        calls[s] = (_unrank_genotype(modes[c], Kc), float(probs[c]), float(pred[c] - norms[s]) if reads[s] else 0.0)
+        if reads[s]:
+            alone += norms[s]
+    return float(log_z - alone), calls
+
+
+def family_calls_host(units, samples, ploidy_of, inbreeding_of, cross, backend, budget=None):
+    """The definition of the family calls over a block, in float64 on `backend` (an object with the reference's
+    genotype_likelihoods; the oracle in the CPU tests): for every called record that needs the kernel, family_unit of the parents'
+    and the progeny's likelihoods under their calling priors (inbreeding_of(sample), the record's locus.frequencies).  budget: the
+    device bytes a record's arrays may take (None: no bound here).  Returns {record index: (INFO FLBF, {sample: (genotype tuple, its
+    probability, FLBF -- None for a parent)}) -- or None where it is not formed: a refused shape, a record beyond the budget, a
+    null record (family_unit)}."""
+    P, Q, progeny, Kc = cross.resolve(samples, ploidy_of)
+    KP, KQ = int(ploidy_of(P)), int(ploidy_of(Q))
+    out = {}
+    for ri, unit in enumerate(units):
+        if not unit["needs_kernel"] or unit["invalid"] is not None:
+            continue
+        locus = unit["locus"]
+        H = len(locus.haplotypes)
+        need = _family_record_bytes(H, KP, KQ)
+        if not all(_cross_evaluable(unit, K) for K in (KP, KQ, Kc)) or need < 0 or (budget is not None and need > budget):
+            out[ri] = None
+            continue
+        reads = {s: len(unit["reads"][s]["counts"]) > 0 for s in progeny}
+        llk = {s: _unit_llk(unit, s, int(ploidy_of(s)), backend) for s in [P, Q] + progeny}
+        fam = family_unit(llk[P], KP, inbreeding_of(P), llk[Q], KQ, inbreeding_of(Q), H, locus.frequencies, cross.gamete_error,
+                          [llk[s] if reads[s] else None for s in progeny])
+        norms = {s: _unit_posterior(llk[s], H, int(ploidy_of(s)), inbreeding_of(s), locus.frequencies)[1] for s in [P, Q] + progeny}
+        out[ri] = _family_result(H, KP, KQ, Kc, P, Q, progeny, reads, fam["mode_p"], fam["prob_p"], fam["mode_q"], fam["prob_q"],
+                                 fam["modes"], fam["probs"], fam["pred"], fam["log_z"], norms)
+    return out
+
+
+def _family_calls_device(units, samples, ploidy_of, inbreeding_of, cross, budget=None):
+    """family_calls_host's result from the device: per shape group one likelihood pass (llks64 alone, cut by the free HBM) and the
+    evidence launch for every unit's own normaliser, the likelihoods kept on the device; then, per number of haplotypes, the
+    records whose arrays fit the budget (device_unit_budget over _family_record_bytes; `budget`: bytes, for the tests) in as few
+    family launches (device.ExactFamily) as the budget allows.  The results are read back after everything is enqueued.  A launch
+    the library refuses is run again record by record; a record refused on its own, beyond the budget, or with a unit whose
+    likelihood pass was refused has no call (None) -- it is never an invalid record."""
+    from .device import ExactFamily, ExactModelEvidence
+
+    P, Q, progeny, Kc = cross.resolve(samples, ploidy_of)
+    KP, KQ = int(ploidy_of(P)), int(ploidy_of(Q))
+    family = [P, Q] + progeny
+    out, llk, norm, pending = {}, {}, {}, []
+    ev = fam = None
+    for shape, group in _shape_groups(units, ploidy_of).items():
+        M, A, H, K = shape
+        group = [key for key in group if units[key[0]]["invalid"] is None and key[1] in family and _cross_evaluable(units[key[0]], K)
+                 and len(units[key[0]]["reads"][key[1]]["counts"]) > 0]
+        for flat in (True, False):
+            todo = [[key for key in group if (inbreeding_of(key[1]) is None) == flat]]
+            while todo:
+                part = todo.pop(0)
+                if not part:
+                    continue
+                for chunk, batch in _estimate_group_batches(units, part, shape, lambda s: 0.0, 8, prior=False):
+                    recs = sorted({ri for ri, _ in chunk})
+                    row = {ri: i for i, ri in enumerate(recs)}
+                    try:
+                        if batch is None:
+                            raise NotImplementedError
+                        llks = batch.run_llks64()
+                        if ev is None:
+                            ev = ExactModelEvidence()
+                        grid = None if flat else np.array([[inbreeding_of(s)] for _, s in chunk], dtype=np.float64)
+                        got = ev.add_group(llks, H, K, grid, [row[ri] for ri, _ in chunk], np.stack([units[ri]["locus"].frequencies for ri in recs]))
+                        table = llks.view(len(chunk), -1)
+                        for i, key in enumerate(chunk):
+                            llk[key], norm[key] = table[i], (got, i)
+                    except NotImplementedError:
+                        if len(chunk) > 1:
+                            todo.extend([key] for key in chunk)   # (a refused chunk again unit by unit; one refused on its own has no likelihoods)
+    by_haps = {}
+    for ri, unit in enumerate(units):
+        if unit["needs_kernel"] and unit["invalid"] is None:
+            by_haps.setdefault(len(unit["locus"].haplotypes), []).append(ri)
+    if budget is None:
+        budget = device_unit_budget(1, most=1 << 62)
+    for H, recs in by_haps.items():
+        need = _family_record_bytes(H, KP, KQ)
+        reads = {ri: {s: len(units[ri]["reads"][s]["counts"]) > 0 for s in family} for ri in recs}
+        ready = []
+        for ri in recs:
+            have = all((ri, s) in llk for s in family if reads[ri][s])
+            if not all(_cross_evaluable(units[ri], K) for K in (KP, KQ, Kc)) or need < 0 or need > budget or not have:
+                out[ri] = None
+            else:
+                ready.append(ri)
+        if not ready:
+            continue
+        if fam is None:
+            fam = ExactFamily()
+        torch = fam.torch
+        zeros = {}
+
+        def table(ri, s, K):
+            if (ri, s) in llk:
+                return llk[(ri, s)]
+            if K not in zeros:   # (a sample without reads: the likelihood of no reads, as _unit_llk)
+                zeros[K] = torch.zeros(ExactFamily._shape(H, K), dtype=torch.float64, device=fam.device)
+            return zeros[K]
+
+        todo = list(_blocks(ready, max(1, int(budget // max(need, 1)))))
+        while todo:
+            part = todo.pop(0)
+            F = [None if inbreeding_of(s) is None else [inbreeding_of(s)] * len(part) for s in (P, Q)]
+            try:
+                got = fam.call(torch.stack([table(ri, P, KP) for ri in part]).reshape(-1), torch.stack([table(ri, Q, KQ) for ri in part]).reshape(-1),
+                               torch.stack([table(ri, s, Kc) for ri in part for s in progeny]).reshape(-1) if progeny else None, H, KP, KQ,
+                               np.stack([units[ri]["locus"].frequencies for ri in part]), cross.gamete_error, F[0], F[1],
+                               np.array([[1 if reads[ri][s] else 0 for s in progeny] for ri in part], dtype=np.int32).reshape(len(part), len(progeny)))
+                pending.append((part, reads, got))
+            except NotImplementedError:
+                if len(part) > 1:
+                    todo.extend([ri] for ri in part)
+                else:
+                    out[part[0]] = None
+    host_norm = {}
+    for part, reads, got in pending:
+        g = {k: v.cpu().numpy() for k, v in got.items()}
+        for i, ri in enumerate(part):
+            H = len(units[ri]["locus"].haplotypes)
+            norms = {}
+            for s in family:
+                if (ri, s) in norm:
+                    t, at = norm[(ri, s)]
+                    if id(t) not in host_norm:
+                        host_norm[id(t)] = (t, t.cpu().numpy())
+                    norms[s] = float(host_norm[id(t)][1][at, 0])
+                else:   # (no reads: the evidence of nothing, log of the prior's total mass; taken as 0 for a progeny)
+                    norms[s] = _unit_posterior(np.zeros(ExactFamily._shape(H, int(ploidy_of(s)))), H, int(ploidy_of(s)), inbreeding_of(s),
+                                               units[ri]["locus"].frequencies)[1]
+            out[ri] = _family_result(H, KP, KQ, Kc, P, Q, progeny, reads[ri], g["mode_p"][i], g["prob_p"][i], g["mode_q"][i], g["prob_q"][i],
+                                     g["mode_c"][i], g["prob_c"][i], g["pred"][i], g["log_z"][i], norms)
+    return out
+
+
+FAMILY_FIELDS = (("FGT", "String", "Genotype called jointly with the family of the cross of %s and %s"),
+                 ("FGPM", "Float", "Posterior probability of FGT in the joint posterior of the family"),
+                 ("FLBF", "Float", "Natural log Bayes factor of the sample's reads given the rest of the family against its calling prior"))
+FAMILY_INFO = ("FLBF", "Float", "Natural log Bayes factor of the family of the cross against unrelated samples")
+
+
+class FamilyCalls:
+    """The writer of `call-exact --family-calls`: the run's own VCF -- header and record lines as the run writes them -- with
+    three FORMAT fields and one INFO field added.  For the two parents and the progeny of the cross, FGT is the first maximum of
+    the sample's marginal in the exact joint posterior of the family (family_unit: post_P, post_Q or q_c) and FGPM its probability;
+    FLBF, for the progeny alone ('.' for the parents), is the natural log Bayes factor of the sample's reads given the rest of the
+    family against the same reads under its own calling prior -- the predictive log evidence minus the evidence of the unit --,
+    and INFO/FLBF that of the whole family against everyone unrelated.  Samples outside the family carry '.' in all three; so does
+    every sample, with no INFO/FLBF, in an invalid record (FILTER=LIMIT among them), for a shape the library refuses, for a record
+    whose [G_P][G_Q] array is beyond the device budget, and for a null record (a family member without a finite genotype, or a
+    joint without mass).  A progeny without reads is called from the rest of the family: FLBF 0.  A record with a single
+    haplotype needs no kernel: FGT all 0, FGPM 1, FLBF 0.  It is not call-pedigree: one nuclear family, no double reduction, one
+    cross a run, no selfing, no grandparents.
+
+    samples: the source's; parents, progeny, gamete_error: as CrossCalls; header_lines: the header of the run's VCF; budget: the
+    device bytes a record's arrays may take (None: a share of the free memory)."""
+
+    def __init__(self, samples, parents, progeny=None, gamete_error=0.01, header_lines=(), budget=None):
+        self.samples = list(samples)
+        self.cross = Cross(parents, progeny, gamete_error)
+        self.header_lines = list(header_lines)
+        self.budget = budget
+        self.lines = []
+
+    def add_block(self, units, lines, ploidy_of, inbreeding_of, backend=None):
+        """The records of a block (what _exact_units returned, after they were called) and their record lines as the main VCF
+        shows them: the lines with the added fields are kept.  backend: the definition on that object (family_calls_host); None =
+        the device.  Returns the calls {record index: (INFO FLBF, {sample: (genotype, probability, FLBF or None)}) or None}."""
+        from .io import vcfstr
+
+        P, Q, progeny, Kc = self.cross.resolve(self.samples, ploidy_of)
+        if backend is not None:
+            calls = family_calls_host(units, self.samples, ploidy_of, inbreeding_of, self.cross, backend, self.budget)
+        else:
+            calls = _family_calls_device(units, self.samples, ploidy_of, inbreeding_of, self.cross, self.budget)
+        for ri, (unit, line) in enumerate(zip(units, lines)):
+            call = calls.get(ri)
+            if call is None and unit["invalid"] is None and not unit["needs_kernel"] and len(unit["locus"].haplotypes) == 1:
+                # (a single haplotype: one genotype, under any prior)
+                call = (0.0, {s: ((0,) * int(ploidy_of(s)), 1.0, None if s in (P, Q) else 0.0) for s in [P, Q] + progeny})
+            cols = []
+            for s in self.samples:
+                c = None if call is None or unit["invalid"] is not None else call[1].get(s)
+                if c is None:
+                    cols.append(".:.:.")
+                else:
+                    cols.append("%s:%s:%s" % ("/".join(str(a) for a in c[0]), vcfstr(c[1]), "." if c[2] is None else "%.3f" % (c[2] + 0.0)))
+            f = line.split("\t")
+            if call is not None and unit["invalid"] is None:
+                add = "FLBF=%.3f" % (call[0] + 0.0)
+                f[7] = add if f[7] in (".", "") else f[7] + ";" + add
+            f[8] += ":FGT:FGPM:FLBF"
+            f[9:] = ["%s:%s" % (col, add) for col, add in zip(f[9:], cols)]
+            self.lines.append("\t".join(f))
+        return calls
+
+    def header(self):
+        """The run's header with the INFO declaration after the last ##INFO line and the three FORMAT ones after the last
+        ##FORMAT line."""
+        out = list(self.header_lines)
+        at = [i for i, ln in enumerate(out) if ln.startswith("##INFO=<")]
+        at = at[-1] + 1 if at else max(len(out) - 1, 0)   # (none declared: before the column line)
+        out.insert(at, '##INFO=<ID=%s,Number=1,Type=%s,Description="%s">' % FAMILY_INFO)
+        at = [i for i, ln in enumerate(out) if ln.startswith("##FORMAT=<")]
+        at = at[-1] + 1 if at else max(len(out) - 1, 0)
+        P, Q = self.cross.parents
+        for k, (name, kind, text) in enumerate(FAMILY_FIELDS):
+            out.insert(at + k, '##FORMAT=<ID=%s,Number=1,Type=%s,Description="%s">' % (name, kind, text % (P, Q) if "%s" in text else text))
+        return out
+
+    def text(self):
+        return "\n".join(self.header() + self.lines) + "\n"
+
+    def write(self, path):
+        with open(path, "w") as fh:
+            fh.write(self.text())
+
+
 def _per_sample(value, samples):
     """A scalar, or a {sample: value} mapping (the reference's per-sample ploidy / inbreeding files), as a function."""
     if isinstance(value, dict):
@@ -1610,7 +1969,8 @@ def _blocks(items, n):
 def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.0024, use_base_phred_scores=False,
                prior_frequencies_tag=None, inbreeding=None, calling=None, filter_input_haplotypes=None, read_kw=None,
                records_per_block=4096, shard=None, block_path=None, estimate_frequencies=None, estimate_tolerance=1e-6,
-               estimate_path=None, model_evidence=None, snv_calls=None, allele_depths=None, cross_calls=None):
+               estimate_path=None, model_evidence=None, snv_calls=None, allele_depths=None, cross_calls=None,
+               family_calls=None):
     """`mchap call-exact` over a VCF of known haplotypes: yields one VCF record line per input record (no header).
     sample_bams: ordered mapping sample name -> BAM path (or pool -> [(sample, path)], or a ReadSource); ploidy /
     inbreeding: a value or {sample: value}.  The records are processed in blocks: the (record x sample) units of a block
@@ -1650,7 +2010,11 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
 
     cross_calls: a CrossCalls over the source's samples; every block's own lines are handed to it likewise, after the frequency
     estimate, and it adds them with CGT, CGPM and CLBF: the progeny of its cross called under their parents' cross prior (the
-    record lines do not depend on it).  Not with `shard`."""
+    record lines do not depend on it).  Not with `shard`.
+
+    family_calls: a FamilyCalls over the source's samples; every block's own lines are handed to it likewise, and it adds them with
+    FGT, FGPM and FLBF: the parents and the progeny of its cross called jointly (the record lines do not depend on it).  Not with
+    `shard`."""
     from .vcfheader import report_fields
 
     if model_evidence is not None and shard is not None:
@@ -1661,9 +2025,13 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
         raise ValueError("allele_depths runs as a single process: the file is not gathered from several ranks (shard)")
     if cross_calls is not None and shard is not None:
         raise ValueError("cross_calls runs as a single process: the file is not gathered from several ranks (shard)")
+    if family_calls is not None and shard is not None:
+        raise ValueError("family_calls runs as a single process: the file is not gathered from several ranks (shard)")
     source = _source(sample_bams, base_error_rate, use_base_phred_scores, read_kw)
     block_path = _call_block_path(block_path, source)
     samples = source.samples
+    if family_calls is not None and list(family_calls.samples) != list(samples):
+        raise ValueError("family_calls: its samples are not the source's")
     if allele_depths is not None and list(allele_depths.samples) != list(samples):
         raise ValueError("allele_depths: its samples are not the source's")
     if cross_calls is not None and list(cross_calls.samples) != list(samples):
@@ -1693,7 +2061,7 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
             alts = unit["locus"].sequences[1:]  # (the input's, minus the alleles --filter-input-haplotypes removed)
             alt = ",".join(alts) if alts else "."
             line = "\t".join([rec["chrom"], str(rec["pos"]), rec["id"], rec["ref"], alt, ".", flt, info, fmt] + [cols[s] for s in samples])
-            if snv_calls is None and allele_depths is None and cross_calls is None:
+            if snv_calls is None and allele_depths is None and cross_calls is None and family_calls is None:
                 yield line
             else:
                 lines.append(line)
@@ -1703,6 +2071,8 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
             allele_depths.add_block(units, lines, ploidy_of, inbreeding_of, calling)
         if cross_calls is not None:
             cross_calls.add_block(units, lines, ploidy_of, inbreeding_of, calling)
+        if family_calls is not None:
+            family_calls.add_block(units, lines, ploidy_of, inbreeding_of, calling)
         yield from lines
 
 

@@ -17,6 +17,7 @@ __all__ = [
     "allele_read_support",
     "cross_genotype_prior",
     "cross_genotype_posteriors",
+    "family_genotype_posteriors",
     "genotype_likelihoods",
     "genotype_posteriors",
     "posterior_allele_frequencies",
@@ -270,6 +271,45 @@ def cross_genotype_posteriors(llks, log_cross_prior):
     G = int(llk.numel())
     # (the shape is given by the arrays alone: any (H, K) with C(H + K - 1, K) = G streams them alike -- K = 1 over G alleles)
     return dev.posteriors(llk, G, 1, lx, [0], full=True)[4][0].cpu().numpy()
+
+
+def family_genotype_posteriors(llks_p, ploidy_p, llks_q, ploidy_q, llks_progeny, n_alleles, log_prior_p=None, log_prior_q=None,
+                               gamete_error=(0, 0), frequencies=None):
+    """The joint call of one nuclear family (not a reference function; the definition: application.family_unit): parents with log
+    likelihoods llks_p [G_p], llks_q [G_q] (VCF order, even ploidies, n_alleles haplotypes) and log genotype priors log_prior_p /
+    _q [G] (None: the flat genotype prior), progeny with log likelihoods llks_progeny[c] [G_c] of ploidy ploidy_p / 2 +
+    ploidy_q / 2 (None for a progeny without reads: it informs nothing and is called from the rest of the family);
+    gamete_error (e_p, e_q) mixes the multinomial of `frequencies` [n_alleles] (None: flat) into the gametes.  Returns
+    (post_p [G_p], post_q [G_q], [q_c [G_c]], log_z, pred [n]): the parents' and the progeny's marginals in the exact joint
+    posterior, the log evidence of the family, and every progeny's predictive log evidence given the rest of the family.  All NaN
+    where the joint has no mass: a sample without a finite genotype, or parents that cannot have a progeny at a gamete error of 0."""
+    import torch
+    from math import log
+
+    from .device import ExactFamily
+
+    H = int(n_alleles)
+    fr = np.full((1, H), 1.0 / H) if frequencies is None else np.asarray(frequencies, dtype=np.float64).reshape(1, H)
+    dev = ExactFamily()
+    tables, shift = [], 0.0
+    for llk, lp in ((llks_p, log_prior_p), (llks_q, log_prior_q)):
+        llk = np.ascontiguousarray(llk, dtype=np.float64)
+        if lp is not None:
+            # (the given prior on top of the flat one the kernel adds: its constant comes off the evidence again)
+            llk = llk + np.asarray(lp, dtype=np.float64)
+            shift += log(len(llk))
+        tables.append(torch.from_numpy(llk).to(dev.device))
+    n = len(llks_progeny)
+    reads = np.array([[0 if x is None else 1 for x in llks_progeny]], dtype=np.int32).reshape(1, n)
+    GC = ExactFamily._shape(H, int(ploidy_p) // 2 + int(ploidy_q) // 2)
+    progeny = None
+    if n:
+        progeny = torch.from_numpy(np.concatenate([np.zeros(GC) if x is None else np.ascontiguousarray(x, dtype=np.float64)
+                                                   for x in llks_progeny])).to(dev.device)
+    got = dev.call(tables[0], tables[1], progeny, H, int(ploidy_p), int(ploidy_q), fr, gamete_error, progeny_reads=reads, full=True)
+    q = got["q"].cpu().numpy()[0]
+    return (got["post_p"].cpu().numpy()[0], got["post_q"].cpu().numpy()[0], [q[c] for c in range(n)],
+            float(got["log_z"].cpu().numpy()[0]) + shift, got["pred"].cpu().numpy()[0])
 
 
 def call_arrays_batch(reads, ploidy, haplotypes, read_counts=None, prior=None, return_arrays=True):

@@ -17,7 +17,8 @@ the VCF, header included, as it is without those flags; so does `call-exact --sn
 SNV-level VCF `atomize` would make of the run's output with GQ, DS and ACP from the exact SNV genotype posteriors
 (application.SnvCalls), and `call-exact --allele-depths FILE`, which writes the run's VCF again with ADP, the posterior expected read
 depth of every allele (application.AlleleDepths), and `call-exact --cross-calls FILE --cross-parents P Q`, which writes the run's VCF
-again with the progeny of that cross called under their parents' cross prior (application.CrossCalls).  `atomize --haplotypes FILE` is host only (mchap_amd/atomize.py)."""
+again with the progeny of that cross called under their parents' cross prior (application.CrossCalls), and `call-exact --family-calls
+FILE --cross-parents P Q`, which writes it with the parents and the progeny called jointly (application.FamilyCalls).  `atomize --haplotypes FILE` is host only (mchap_amd/atomize.py)."""
 import argparse
 import sys
 
@@ -170,8 +171,14 @@ def build_parser(program):
                            help="(not a reference flag) write to FILE, when the run ends, this run's VCF with three FORMAT fields added "
                                 "for the progeny of the cross --cross-parents: CGT, the genotype under the prior the parents' posteriors "
                                 "imply, CGPM, its probability, and CLBF, the log Bayes factor of that prior against the calling prior")
+            p.add_argument("--family-calls", type=str, nargs=1, default=[None], metavar="FILE",
+                           help="(not a reference flag) write to FILE, when the run ends, this run's VCF with the family of the cross "
+                                "--cross-parents called jointly: FORMAT FGT, the genotype of a parent or a progeny in the exact joint "
+                                "posterior of both parents and all progeny, FGPM, its probability, FLBF (progeny), the log Bayes factor "
+                                "of the sample's reads given the rest of the family against its calling prior, and INFO FLBF, that of "
+                                "the family against unrelated samples")
             p.add_argument("--cross-parents", type=str, nargs=2, default=None, metavar=("P", "Q"),
-                           help="(not a reference flag) with --cross-calls: the two parents of the cross, by sample name")
+                           help="(not a reference flag) with --cross-calls or --family-calls: the two parents of the cross, by sample name")
             p.add_argument("--cross-progeny", type=str, nargs="+", default=None, metavar="SAMPLE",
                            help="(not a reference flag) with --cross-calls: the progeny of the cross (default: every other sample whose "
                                 "ploidy is half of P's plus half of Q's)")
@@ -244,7 +251,7 @@ def run(argv, out=None):
                                     read_group_field=id_field, mapping_quality=args.mapping_quality[0],
                                     skip_duplicates=args.skip_duplicates, skip_qcfail=args.skip_qcfail,
                                     skip_supplementary=args.skip_supplementary, workers=args.cores[0])
-    seed = evidence = snv_calls = allele_depths = cross_calls = header = None
+    seed = evidence = snv_calls = allele_depths = cross_calls = family_calls = header = None
     block_path = BLOCK_PATHS[args.block_path]
     if program == "assemble":
         if args.targets[0] is not None and args.region[0] is not None:
@@ -283,17 +290,18 @@ def run(argv, out=None):
                                  "frequencies to estimate")
             evidence = model_evidence_settings(args, samples, inbreeding, tag, estimate, world)
             snv_calls = snv_calls_settings(args, samples, world, ["mchap_amd"] + header_argv)
-            if args.allele_depths[0] is not None or args.cross_calls[0] is not None:
+            if args.allele_depths[0] is not None or args.cross_calls[0] is not None or args.family_calls[0] is not None:
                 header = vcfheader.header_lines(program, ["mchap_amd"] + header_argv, samples, contigs, report=report, random_seed=seed,
                                                 estimate=estimate is not None)
             allele_depths = allele_depths_settings(args, samples, world, header)
             cross_calls = cross_calls_settings(args, samples, ploidy, world, header)
+            family_calls = family_calls_settings(args, samples, ploidy, world, header)
             records = application.call_exact(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
                                              inbreeding=inbreeding, filter_input_haplotypes=args.filter_input_haplotypes[0], shard=shard,
                                              block_path=block_path, estimate_frequencies=estimate,
                                              estimate_tolerance=1e-6 if args.estimate_tolerance[0] is None else args.estimate_tolerance[0],
                                              model_evidence=evidence, snv_calls=snv_calls, allele_depths=allele_depths,
-                                             cross_calls=cross_calls)
+                                             cross_calls=cross_calls, family_calls=family_calls)
         else:
             seed = args.mcmc_seed[0]
             records = application.call(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
@@ -330,6 +338,8 @@ def run(argv, out=None):
         allele_depths.write(args.allele_depths[0])
     if cross_calls is not None:
         cross_calls.write(args.cross_calls[0])
+    if family_calls is not None:
+        family_calls.write(args.family_calls[0])
     return n
 
 
@@ -340,10 +350,12 @@ SNV_FLAGS = ("--snv-calls", "--snv-report")
 ALLELE_DEPTH_FLAGS = ("--allele-depths",)
 # ... and the flags of the cross-calls file
 CROSS_FLAGS = ("--cross-calls", "--cross-parents", "--cross-progeny", "--gamete-error")
+# ... and the flag of the family-calls file, which takes its cross from the three above
+FAMILY_FLAGS = ("--family-calls",)
 
 
 def _header_argv(argv, options):
-    """The command line as the VCF header states it: without the model-evidence, SNV-file, allele-depths and cross-calls flags and their values -- the VCF, header included,
+    """The command line as the VCF header states it: without the model-evidence, SNV-file, allele-depths, cross-calls and family-calls flags and their values -- the VCF, header included,
     is byte for byte what the run writes without them.  options: the parser's option strings; a flag is resolved as argparse
     resolves it (the exact name, else the one option it is a prefix of), so an abbreviated flag is taken out too."""
     out, skipping = [], False
@@ -351,7 +363,7 @@ def _header_argv(argv, options):
         if a.startswith("--"):
             name = a.split("=", 1)[0]
             full = [name] if name in options else [o for o in options if o.startswith(name)]
-            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS + SNV_FLAGS + ALLELE_DEPTH_FLAGS + CROSS_FLAGS
+            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS + SNV_FLAGS + ALLELE_DEPTH_FLAGS + CROSS_FLAGS + FAMILY_FLAGS
         if not skipping:
             out.append(a)
     return out
@@ -412,6 +424,8 @@ def cross_calls_settings(args, samples, ploidy, world, header_lines):
     from . import application
 
     if args.cross_calls[0] is None:
+        if getattr(args, "family_calls", [None])[0] is not None:   # (the cross is --family-calls' then)
+            return None
         for flag, value in (("--cross-parents", args.cross_parents), ("--cross-progeny", args.cross_progeny),
                             ("--gamete-error", args.gamete_error)):
             if value is not None:
@@ -425,6 +439,26 @@ def cross_calls_settings(args, samples, ploidy, world, header_lines):
     if len(error) > 2 or not all(0.0 <= e <= 1.0 for e in error):   # (False for NaN too)
         raise ValueError("--gamete-error: one value, or one for each parent, in [0, 1]")
     calls = application.CrossCalls(samples, args.cross_parents, args.cross_progeny, error, header_lines)
+    calls.cross.resolve(list(samples), application._per_sample(ploidy, samples))
+    return calls
+
+
+def family_calls_settings(args, samples, ploidy, world, header_lines):
+    """The --family-calls flag of call-exact, with the cross of --cross-parents / --cross-progeny / --gamete-error -> an
+    application.FamilyCalls over the run's header lines, or None without --family-calls.  The cross is checked here, before any
+    work, as cross_calls_settings checks it."""
+    from . import application
+
+    if args.family_calls[0] is None:
+        return None
+    if args.cross_parents is None:
+        raise ValueError("--family-calls needs --cross-parents P Q")
+    if world > 1:
+        raise ValueError("--family-calls runs as a single process: the file is not gathered from several ranks (WORLD_SIZE > 1)")
+    error = [0.01] if args.gamete_error is None else list(args.gamete_error)
+    if len(error) > 2 or not all(0.0 <= e <= 1.0 for e in error):   # (False for NaN too)
+        raise ValueError("--gamete-error: one value, or one for each parent, in [0, 1]")
+    calls = application.FamilyCalls(samples, args.cross_parents, args.cross_progeny, error, header_lines)
     calls.cross.resolve(list(samples), application._per_sample(ploidy, samples))
     return calls
 

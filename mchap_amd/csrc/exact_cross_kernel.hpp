@@ -47,19 +47,16 @@ inline size_t exact_gamete_lds(int H, int K) {
   return ((size_t)H * (K + 1) + (K + 1) + (size_t)H + 1 + (CROSS_BIN * CROSS_BIN + 1) / 2) * 8;
 }
 
-template <int KM = 8>
-__global__ __launch_bounds__(EXACT_THREADS) void exact_gamete_kernel(const ExactGameteParams P) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  const int unit = blockIdx.x / P.nblk, blk = blockIdx.x % P.nblk;
-  const int H = P.H, K = P.K, T = P.T, KR = P.K - P.T;
-  const bool has_prior = P.inbreeding != nullptr;
+// The LDS tables of a unit of ploidy K over H haplotypes with frequencies fr [H] (exact_gamete_lds bytes at smem): the prior tables
+// of exact_setup at inbreeding F (has_prior; the flat genotype prior has none), the frequencies themselves, and the binomials
+// bin[n * CROSS_BIN + k] = C(n, k).  Ends with the workgroup's barrier.
+__device__ __forceinline__ void cross_setup(unsigned char *smem, int H, int K, bool has_prior, double F, const double *fr, PriorTab &pt,
+                                            int *&bin) {
   double *lgd = reinterpret_cast<double *>(smem);  // [H][K + 1]
   double *lgf = lgd + (size_t)H * (K + 1);         // [K + 1]
   double *lfreq = lgf + (K + 1);                   // [H]
   double *left = lfreq + H;                        // [1]
-  int *bin = reinterpret_cast<int *>(left + 1);    // [CROSS_BIN][CROSS_BIN]
-  const double *fr = P.freqs + (size_t)P.unit_row[unit] * P.stride;
-  const double F = has_prior ? P.inbreeding[unit] : 0.0;
+  bin = reinterpret_cast<int *>(left + 1);         // [CROSS_BIN][CROSS_BIN]
   if (has_prior) {
     // the prior tables of exact_setup, from the unit's F and its row
     const double scale = (1.0 - F) / F;
@@ -83,7 +80,6 @@ __global__ __launch_bounds__(EXACT_THREADS) void exact_gamete_kernel(const Exact
     bin[q] = b;
   }
   __syncthreads();
-  PriorTab pt;
   pt.lgd = lgd;
   pt.lgf = lgf;
   pt.lfreq = lfreq;
@@ -91,6 +87,20 @@ __global__ __launch_bounds__(EXACT_THREADS) void exact_gamete_kernel(const Exact
   pt.lnH = 0.0;
   pt.F = F;
   pt.has_freqs = 1;
+}
+
+template <int KM = 8>
+__global__ __launch_bounds__(EXACT_THREADS) void exact_gamete_kernel(const ExactGameteParams P) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int unit = blockIdx.x / P.nblk, blk = blockIdx.x % P.nblk;
+  const int H = P.H, K = P.K, T = P.T, KR = P.K - P.T;
+  const bool has_prior = P.inbreeding != nullptr;
+  const double *fr = P.freqs + (size_t)P.unit_row[unit] * P.stride;
+  const double F = has_prior ? P.inbreeding[unit] : 0.0;
+  PriorTab pt;
+  int *bin;
+  cross_setup(smem, H, K, has_prior, F, fr, pt, bin);
+  const double *lfreq = pt.lfreq;
   const double norm = P.log_norm[unit];
   const bool finite_norm = norm > -INFINITY && norm < INFINITY;
   const double flat = has_prior ? 0.0 : -log((double)P.G);
@@ -167,24 +177,10 @@ inline size_t exact_cross_prior_lds(long long NAP, long long NAQ) {
   return (size_t)(NAP + NAQ) * 8;
 }
 
-template <int KM = 8>
-__global__ __launch_bounds__(EXACT_THREADS) void exact_cross_prior_kernel(const ExactCrossPriorParams P) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  const int row = blockIdx.x / P.nblk, blk = blockIdx.x % P.nblk;
-  const int TP = P.TP, KC = P.TP + P.TQ;
-  const double *gp = P.gam_p + (size_t)row * P.NAP, *gq = P.gam_q + (size_t)row * P.NAQ;
-  if (P.staged) {
-    double *tp = reinterpret_cast<double *>(smem), *tq = tp + P.NAP;
-    for (int i = threadIdx.x; i < P.NAP; i += EXACT_THREADS) tp[i] = gp[i];
-    for (int i = threadIdx.x; i < P.NAQ; i += EXACT_THREADS) tq[i] = gq[i];
-    __syncthreads();
-    gp = tp;
-    gq = tq;
-  }
-  const long long j = (long long)blk * EXACT_THREADS + threadIdx.x;
-  if (j >= P.GC) return;
-  int gc[KM];
-  unrank_genotype(j, KC, gc);
+// The distinct sub-multisets a of TP alleles of the ascending multiset gc [KC], in VCF order of a: f(ra, rb, x, cn, m) with the
+// ranks of a and of gc - a, and -- over the m distinct alleles of gc, ascending -- a's copies x[i] out of gc's cn[i].
+template <int KM, class Fn>
+__device__ __forceinline__ void for_each_submultiset(const int (&gc)[KM], int KC, int TP, Fn f) {
   // the distinct alleles of gc, ascending, and their dosages
   int al[KM], cn[KM], x[KM];
   int m = 0;
@@ -203,7 +199,6 @@ __global__ __launch_bounds__(EXACT_THREADS) void exact_cross_prior_kernel(const 
     x[i] = cn[i] < rem ? cn[i] : rem;
     rem -= x[i];
   }
-  double sum = 0.0;
   for (;;) {
     long long ra = 0, rb = 0;
     int pa = 0, pb = 0;
@@ -211,7 +206,7 @@ __global__ __launch_bounds__(EXACT_THREADS) void exact_cross_prior_kernel(const 
       for (int d = 0; d < x[i]; d++) ra += cwr(al[i], ++pa);
       for (int d = x[i]; d < cn[i]; d++) rb += cwr(al[i], ++pb);
     }
-    sum += gp[ra] * gq[rb];
+    f(ra, rb, x, cn, m);
     // the successor: the lowest allele that can take one more copy from the alleles below it; those then as low as can be
     int s = x[0], i = 1;
     while (i < m && !(x[i] < cn[i] && s >= 1)) {
@@ -226,6 +221,28 @@ __global__ __launch_bounds__(EXACT_THREADS) void exact_cross_prior_kernel(const 
       rem -= x[q];
     }
   }
+}
+
+template <int KM = 8>
+__global__ __launch_bounds__(EXACT_THREADS) void exact_cross_prior_kernel(const ExactCrossPriorParams P) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int row = blockIdx.x / P.nblk, blk = blockIdx.x % P.nblk;
+  const int TP = P.TP, KC = P.TP + P.TQ;
+  const double *gp = P.gam_p + (size_t)row * P.NAP, *gq = P.gam_q + (size_t)row * P.NAQ;
+  if (P.staged) {
+    double *tp = reinterpret_cast<double *>(smem), *tq = tp + P.NAP;
+    for (int i = threadIdx.x; i < P.NAP; i += EXACT_THREADS) tp[i] = gp[i];
+    for (int i = threadIdx.x; i < P.NAQ; i += EXACT_THREADS) tq[i] = gq[i];
+    __syncthreads();
+    gp = tp;
+    gq = tq;
+  }
+  const long long j = (long long)blk * EXACT_THREADS + threadIdx.x;
+  if (j >= P.GC) return;
+  int gc[KM];
+  unrank_genotype(j, KC, gc);
+  double sum = 0.0;
+  for_each_submultiset<KM>(gc, KC, TP, [&](long long ra, long long rb, const int *, const int *, int) { sum += gp[ra] * gq[rb]; });
   P.log_x[(size_t)row * P.GC + j] = log(sum);  // (exactly -inf where every product is 0)
 }
 

@@ -990,6 +990,95 @@ class ExactCross:
         return (log_z, mode, prob, norm, post) if full else (log_z, mode, prob, norm)
 
 
+class ExactFamily:
+    """The parents and the progeny of one cross called jointly for exact-caller units whose likelihoods are resident on the device
+    (mchap_exact_family_device): per record the exact joint posterior of the two parents and all progeny, its marginals and every
+    progeny's predictive log evidence.  The definition: application.family_unit."""
+
+    def __init__(self, device=None):
+        self.torch = _torch()
+        self.device = _device(self.torch, device)
+        self.launches = 0      # calls enqueued
+
+    _tensor = ExactModelEvidence._tensor
+    _shape = staticmethod(ExactCross._shape)
+
+    @staticmethod
+    def workspace_bytes(n_records, n_haps, ploidy_p, ploidy_q, force_fallback=False):
+        """The bytes of workspace a call over n_records records needs (the [G_P][G_Q] array of every record and the smaller
+        stages), or -1 for a shape the kernels refuse."""
+        return int(_lib.lib().mchap_exact_family_workspace_bytes(int(n_records), int(n_haps), int(ploidy_p), int(ploidy_q),
+                                                                 1 if force_fallback else 0))
+
+    def call(self, llks_p, llks_q, llks_c, n_haps, ploidy_p, ploidy_q, freqs, gamete_error=(0.01, 0.01), inbreeding_p=None,
+             inbreeding_q=None, progeny_reads=None, full=False, force_fallback=False, workspace_limit=None):
+        """The records of one shape, enqueued on torch's current stream.  llks_p [R * G_P], llks_q [R * G_Q], llks_c
+        [R * n * G_c] float64 tensors on the device (llks_c None or empty: no progeny); freqs [R, stride >= n_haps] the records'
+        calling frequencies; gamete_error (e_P, e_Q), each a scalar or [R], every e in [0, 1]; inbreeding_p / _q [R] (or a
+        scalar), every F in [0, 1), or None: the flat genotype prior; progeny_reads [R, n] of 0 / 1 (None: every progeny has
+        reads).  F and e are checked here, on the host copies.  workspace_limit: the bytes the caller offers (None: what the device
+        has free); a workspace beyond it, or a shape the library refuses: NotImplementedError.  Returns a dict of tensors on the
+        device: post_p [R, G_P], post_q [R, G_Q], mode_p, mode_q [R] int64 (-1: a null record), prob_p, prob_q [R], log_z [R],
+        mode_c [R, n] int64, prob_c [R, n], pred [R, n], and with full=True q [R, n, G_c]."""
+        torch, dev = self.torch, self.device
+        H, KP, KQ = int(n_haps), int(ploidy_p), int(ploidy_q)
+        if KP < 2 or KQ < 2 or KP % 2 or KQ % 2:
+            raise ValueError("family: parents of even ploidy are needed, got %d and %d" % (KP, KQ))
+        GP, GQ, GC = self._shape(H, KP), self._shape(H, KQ), self._shape(H, KP // 2 + KQ // 2)
+        assert llks_p.dtype == torch.float64 and llks_p.is_contiguous() and llks_p.numel() % GP == 0
+        R = llks_p.numel() // GP
+        assert llks_q.dtype == torch.float64 and llks_q.is_contiguous() and llks_q.numel() == R * GQ
+        n = 0
+        if llks_c is not None and llks_c.numel():
+            assert llks_c.dtype == torch.float64 and llks_c.is_contiguous() and R > 0 and llks_c.numel() % (R * GC) == 0
+            n = llks_c.numel() // (R * GC)
+        d_fr = self._tensor(freqs, torch.float64, np.float64)
+        assert d_fr.dim() == 2 and int(d_fr.shape[0]) == R and int(d_fr.shape[1]) >= H
+        errs, Fs = [], []
+        for e in gamete_error:
+            e = np.array(np.broadcast_to(np.asarray(e, dtype=np.float64), (R,)))
+            if not np.all((e >= 0.0) & (e <= 1.0)):
+                raise ValueError("gamete_error: every e must lie in [0, 1]")
+            errs.append(torch.from_numpy(e).to(dev))
+        for F in (inbreeding_p, inbreeding_q):
+            if F is not None:
+                F = np.array(np.broadcast_to(np.asarray(F, dtype=np.float64), (R,)))
+                if not np.all((F >= 0.0) & (F < 1.0)):   # (False for NaN and infinities too)
+                    raise ValueError("inbreeding: every F must lie in [0, 1)")
+                F = torch.from_numpy(F).to(dev)
+            Fs.append(F)
+        d_reads = None
+        if progeny_reads is not None and n:
+            reads = np.ascontiguousarray(progeny_reads, dtype=np.int32)
+            assert reads.shape == (R, n)
+            d_reads = torch.from_numpy(reads).to(dev)
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)          # noqa: E731
+        i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device=dev)            # noqa: E731
+        out = dict(post_p=f64(R, GP), post_q=f64(R, GQ), mode_p=i64(R), mode_q=i64(R), prob_p=f64(R), prob_q=f64(R), log_z=f64(R),
+                   mode_c=i64(R, n), prob_c=f64(R, n), pred=f64(R, n))
+        if R == 0:
+            if full:
+                out["q"] = f64(0, n, GC)
+            return out
+        wsb = self.workspace_bytes(R, H, KP, KQ, force_fallback)
+        free, _ = torch.cuda.mem_get_info()
+        limit = free if workspace_limit is None else min(int(workspace_limit), free)
+        if wsb < 0 or wsb + (R * n * GC * 8 if full else 0) > limit:
+            raise NotImplementedError("mchap_hip: family of %d records, ploidies %d x %d over %d haplotypes: the shape is refused, or "
+                                      "its [G_P][G_Q] workspace is beyond what is offered" % (R, KP, KQ, H))
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+        if full:
+            out["q"] = f64(R, n, GC)
+        _lib.check(_lib.lib().mchap_exact_family_device(
+            R, n, _ptr(llks_p), _ptr(llks_q), _ptr(llks_c) if n else None, _ptr(d_reads), H, KP, KQ, _ptr(Fs[0]), _ptr(Fs[1]),
+            _ptr(d_fr), int(d_fr.shape[1]), _ptr(errs[0]), _ptr(errs[1]), _ptr(out["post_p"]), _ptr(out["mode_p"]), _ptr(out["prob_p"]),
+            _ptr(out["post_q"]), _ptr(out["mode_q"]), _ptr(out["prob_q"]), _ptr(out["q"]) if full else None,
+            _ptr(out["mode_c"]) if n else None, _ptr(out["prob_c"]) if n else None, _ptr(out["pred"]) if n else None, _ptr(out["log_z"]),
+            _ptr(ws), C.c_int64(wsb), 1 if force_fallback else 0, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        self.launches += 1
+        return out
+
+
 class DenovoRaggedBatch(_OwnBuffers):
     """Units of different shapes (loci with different numbers of SNVs and alleles, samples with different read depths,
     per-sample ploidy / inbreeding) in ONE sampler launch, with the posterior summary and the replicate incongruence
