@@ -515,6 +515,36 @@ int mchap_exact_family_device(int n_records, int n_progeny, const double *llks_p
                               double *pred_log_evidence, double *log_z_fam, void *workspace, int64_t workspace_bytes,
                               int force_fallback, void *stream);
 
+/* Candidate parent pairs per progeny (call-exact --parentage): the cross evidence of every progeny of a record under every pair of
+ * rows of two gamete tables, from one pass over the pairs of gametes.  n_records records of one shape -- n_haps haplotypes, n_a rows
+ * of gametes of t_a haplotypes, n_b rows of gametes of t_b, n_progeny progeny of ploidy t_a + t_b each; multisets in VCF order:
+ *   log_z[r][c][i][j] = m_c + log sum_a gametes_a[r][i][a] sum_b gametes_b[r][j][b] exp(llks_c[r][c][rank(a + b)] - m_c),  m_c = max llks_c[r][c].
+ * The entry takes gamete SIZES, not ploidies: a row is any distribution over the gametes -- a candidate's row from
+ * mchap_exact_gametes_device, or the unknown parent's Mult(a; t, f), which is what that entry returns at a gamete error of 1 and
+ * which mchap_exact_parentage_population_device forms here with a small kernel of its own (the arithmetic of the gamete kernel's
+ * multinomial, bit for bit; no likelihoods of a parent of ploidy 2t are needed): rows[r * row_pitch + a] = Mult(a; t, frequencies[r]),
+ * so that it can be written into a row of a table.  gametes_a and gametes_b may be the same table.  For rows (i, j) from
+ * mchap_exact_gametes_device at the parents' gamete errors, log_z is the log_z of mchap_exact_cross_posterior_device under the
+ * cross prior of mchap_exact_cross_prior_device.
+ * progeny_reads int32 [R][n_progeny] (NULL: all 1): a progeny with 0 has no reads -- its likelihoods are not read and every entry is
+ * exactly 0.  A NaN row (a candidate without a finite genotype) makes its row or column of log_z NaN and nothing else; a progeny
+ * with a NaN likelihood, or without a finite one, has NaN throughout; an entry whose every product is 0 is exactly -inf.
+ * Gather form: one owning lane per output cell, no atomics.  One lane owns a gamete a and adds its terms over b in VCF order, one
+ * after the other; the sum over a is taken by 256 lanes, lane l adding a = l, l + 256, ... in that order, then the wavefront's
+ * butterfly (32, 16, 8, 4, 2, 1), then the four wavefronts in order.  Equal inputs give equal bits whatever the place of a record in
+ * the call, and an entry's bits do not depend on how many other rows or progeny the call holds, on their order, or on the kernel's
+ * chunks of 16 columns.  `workspace`: mchap_exact_parentage_workspace_bytes (the sums over b of every (progeny, column, gamete a));
+ * -1, with the call itself MCHAP_ERR_LIMIT, for a gamete size outside 1..7, a progeny ploidy beyond MCHAP_MAX_PLOIDY_DENOVO, 2^62
+ * genotypes or more, or n_haps x (t_a + t_b) rank terms beyond the LDS beside the staged rows (n_haps above about 16000 / (t_a +
+ * t_b)).  A workspace smaller than asked is MCHAP_ERR_LIMIT: nothing is allocated behind the caller's back.  Any n_a, n_b >= 1.
+ * Enqueue on `stream`, no synchronisation. */
+int64_t mchap_exact_parentage_workspace_bytes(int n_records, int n_progeny, int n_a, int n_b, int n_haps, int t_a, int t_b);
+int mchap_exact_parentage_device(int n_records, int n_progeny, int n_a, int n_b, const double *gametes_a, const double *gametes_b,
+                                 const double *llks_c, const int32_t *progeny_reads, int n_haps, int t_a, int t_b, double *log_z,
+                                 void *workspace, int64_t workspace_bytes, void *stream);
+int mchap_exact_parentage_population_device(int n_records, const double *frequencies, int stride, int n_haps, int t, double *rows,
+                                            int64_t row_pitch, void *stream);
+
 /* Summaries of given posterior arrays [U][G] (calling.exact.posterior_allele_frequencies 332-369, the sum of
  * alternate_dosage_posteriors 372-407 for the array's mode): device pointers, any output may be NULL. */
 int mchap_exact_posterior_summaries_batch_device(int n_units, const double *posteriors, int64_t n_genotypes, int ploidy,

@@ -1204,7 +1204,7 @@ def gamete_table(p, H, K, f, error):
         gam'[a] = (1 - error) gam[a] + error Mult(a; t, f)
     (reference mchap/assemble/inheritence.py gamete_probabilities, mchap/pedigree/prior.py gamete_log_pmf with lambda = 0 and
     log_unknown_dosage_prior).  The order of every sum and product is the kernel's (exact_gamete_kernel)."""
-    from math import comb, factorial
+    from math import comb
 
     if K < 2 or K % 2:
         raise ValueError("a parent of ploidy %d: the gametes of an even ploidy alone are formed" % K)
@@ -1222,11 +1222,23 @@ def gamete_table(p, H, K, f, error):
         pg = p[_multiset_ranks(g)]
         total += np.where(pg > 0.0, pg, 0.0) * w
     gam = total / comb(K, t)
+    return (1.0 - error) * gam + error * population_gametes(H, t, f)
+
+
+def population_gametes(H, t, f):
+    """float64 [C(H + t - 1, t)]: Mult(a; t, f) of every gamete of t haplotypes out of H -- the gamete distribution of a parent
+    nothing is known of but the population's frequencies f [H], what gamete_table gives at a gamete error of 1.  The multinomial
+    coefficient is exact; the frequencies are multiplied in the order of a (exact_gamete_kernel, parentage_mult_kernel)."""
+    from math import factorial
+
+    f = np.asarray(f, dtype=np.float64)
+    a = _genotype_table(H, t)
+    da = _dosages(a, H)
     coef = np.array([factorial(t) // int(np.prod([factorial(int(x)) for x in row])) for row in da], dtype=np.float64)
     pf = np.ones(len(a))
     for i in range(t):
         pf = pf * f[a[:, i]]
-    return (1.0 - error) * gam + error * (coef * pf)
+    return coef * pf
 
 
 def cross_prior_tables(p_p, K_p, p_q, K_q, H, gamete_error=(0.0, 0.0), f=None):
@@ -1895,6 +1907,456 @@ class FamilyCalls:
             fh.write(self.text())
 
 
+# ---------------------------------------------------------------------------------------------------------
+# call-exact --parentage: every pair of candidate parents ranked per progeny by the evidence of the closed-form cross model
+# ---------------------------------------------------------------------------------------------------------
+PARENTAGE_TMAX = 7          # the largest gamete size the parentage kernel takes (exact_parentage_kernel.hpp)
+PARENTAGE_LDS = 160 * 1024  # ... and the LDS its rank table shares with PARENTAGE_STAGE bytes of staged rows
+PARENTAGE_STAGE = 16 * 256 * 8
+UNKNOWN_PARENT = "."
+
+
+def parentage_unit(gametes_a, gametes_b, llk_c, H, t_a, t_b):
+    """The definition of the parentage evidence of one progeny at one record, in float64, in the kernel's order
+    (exact_parentage_kernel.hpp): float64 [n_a, n_b],
+        log_z[i][j] = m + log sum_a gametes_a[i][a] sum_b gametes_b[j][b] exp(llk_c[rank(a + b)] - m),  m = max llk_c,
+    for gamete rows gametes_a [n_a, NA] of t_a haplotypes and gametes_b [n_b, NB] of t_b (gamete_table, population_gametes) and the
+    progeny's log likelihoods llk_c [G_c] of ploidy t_a + t_b -- the cross evidence log sum_gc X_ij[gc] exp(llk_c[gc]) of
+    cross_prior_unit, for every pair of rows from one table T[a][b] = exp(llk_c[rank(a + b)] - m) (gamete_pair_ranks).  The sum
+    over b takes its terms in VCF order, one after the other; the sum over a as 256 strided partial sums (a = l, l + 256, ...),
+    then the butterfly over each 64 of them (32, 16, 8, 4, 2, 1), then the four results in order.  llk_c None: a progeny without
+    reads, every entry exactly 0.  A NaN row gives NaN in its row or column alone; a NaN likelihood, or none that is finite, NaN
+    throughout; an entry whose every product is 0 is exactly -inf."""
+    A = np.atleast_2d(np.asarray(gametes_a, dtype=np.float64))
+    B = np.atleast_2d(np.asarray(gametes_b, dtype=np.float64))
+    if llk_c is None:
+        return np.zeros((len(A), len(B)))
+    llk = np.asarray(llk_c, dtype=np.float64)
+    rank = gamete_pair_ranks(H, t_a, t_b)
+    NA, NB = rank.shape
+    assert A.shape[1] == NA and B.shape[1] == NB
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        m = float("nan") if np.any(np.isnan(llk)) else float(np.max(llk))
+        T = np.exp(llk[rank] - m)
+        W = np.zeros((NA, len(B)))
+        for b in range(NB):
+            W = W + T[:, b, None] * B[None, :, b]
+        lanes, wave = 256, 64
+        part = np.zeros((lanes, len(A), len(B)))
+        for lo in range(0, NA, lanes):
+            n = min(lanes, NA - lo)
+            part[:n] = part[:n] + A.T[lo:lo + n, :, None] * W[lo:lo + n, None, :]
+        v = part.reshape(lanes // wave, wave, len(A), len(B))
+        lane = np.arange(wave)
+        for o in (32, 16, 8, 4, 2, 1):
+            v = v + v[:, lane ^ o]
+        z = v[0, 0]
+        for w in range(1, lanes // wave):
+            z = z + v[w, 0]
+        return m + np.log(z)
+
+
+def _parentage_shape_ok(H, t_a, t_b):
+    """Whether the parentage launch takes gametes of t_a and t_b haplotypes out of H (mchap_exact_parentage_workspace_bytes >= 0)."""
+    from math import comb
+
+    from ._lib import MAX_PLOIDY_GENERAL
+
+    K = t_a + t_b
+    return (1 <= t_a <= PARENTAGE_TMAX and 1 <= t_b <= PARENTAGE_TMAX and K <= MAX_PLOIDY_GENERAL and comb(H + K - 1, K) < 1 << 62
+            and H * K * 8 + PARENTAGE_STAGE <= PARENTAGE_LDS)
+
+
+class ParentagePlan:
+    """The hypotheses of a parentage run: candidates (sample names, in the order their pairs are listed in), progeny (None: every
+    sample that is not a candidate), checked against the run's samples and ploidies.  hypotheses[c]: the rows of progeny c, in
+    hypothesis order -- every pair (i, j), i < j in candidate order, with t_i + t_j = K_c, then every (i, '.') with 1 <= K_c - t_i,
+    the other gamete the population's, then ('.', '.') --, a pair that holds c itself left out.  launches[K_c]: the (t_a, t_b),
+    t_a <= t_b, the rows of a progeny of ploidy K_c need; where(c, row) = ((t_a, t_b), i, j): the entry of that launch's
+    [n_a + 1, n_b + 1] matrix -- the candidates of a gamete size in candidate order, the population's row last."""
+
+    def __init__(self, samples, candidates, progeny, ploidy_of):
+        samples, candidates = list(samples), list(candidates)
+        progeny = [s for s in samples if s not in candidates] if progeny is None else list(progeny)
+        if not candidates:
+            raise ValueError("parentage: no candidate parent")
+        for what, names in (("candidate", candidates), ("progeny", progeny)):
+            for s in names:
+                if s not in samples:
+                    raise ValueError("parentage: %s %r is not a sample of this run" % (what, s))
+                if names.count(s) > 1:
+                    raise ValueError("parentage: %s %r is named more than once" % (what, s))
+        for s in candidates:
+            if int(ploidy_of(s)) < 2 or int(ploidy_of(s)) % 2:
+                raise ValueError("parentage: candidate %r has ploidy %d: an even ploidy is needed" % (s, int(ploidy_of(s))))
+        self.candidates = candidates
+        self.progeny = [s for s in samples if s in progeny]   # (sample order)
+        self.ploidy = {s: int(ploidy_of(s)) for s in set(candidates) | set(progeny)}
+        self.size = {s: self.ploidy[s] // 2 for s in candidates}
+        self.by_size = {}
+        for s in candidates:
+            self.by_size.setdefault(self.size[s], []).append(s)
+        self.hypotheses, self.launches = {}, {}
+        for c in self.progeny:
+            Kc = self.ploidy[c]
+            rows = [(p, q) for i, p in enumerate(candidates) for q in candidates[i + 1:]
+                    if c not in (p, q) and self.size[p] + self.size[q] == Kc]
+            rows += [(p, UNKNOWN_PARENT) for p in candidates if p != c and Kc - self.size[p] >= 1]
+            self.hypotheses[c] = rows + [(UNKNOWN_PARENT, UNKNOWN_PARENT)]
+            need = self.launches.setdefault(Kc, [])
+            for row in rows:
+                shape = self.where(c, row)[0]
+                if shape not in need:
+                    need.append(shape)
+
+    def index(self, s, t):
+        """The row of candidate s -- or of the unknown parent -- in the table of gamete size t."""
+        return len(self.by_size.get(t, ())) if s == UNKNOWN_PARENT else self.by_size[t].index(s)
+
+    def where(self, c, row):
+        p, q = row
+        tp = self.size[p]
+        tq = self.ploidy[c] - tp if q == UNKNOWN_PARENT else self.size[q]
+        if tp <= tq:
+            return (tp, tq), self.index(p, tp), self.index(q, tq)
+        return (tq, tp), self.index(q, tq), self.index(p, tp)
+
+    def used(self, c):
+        """The candidates in the rows of progeny c."""
+        return [s for s in self.candidates if any(s in row for row in self.hypotheses[c])]
+
+
+def _parentage_need(H, shape, n_b):
+    """Device bytes of one (record, progeny) of a parentage launch: the sums over b of every (column, gamete a), its likelihoods
+    stacked for the launch, and a row of results."""
+    from math import comb
+
+    ta, tb = shape
+    return (n_b * comb(H + ta - 1, ta) + comb(H + ta + tb - 1, ta + tb)) * 8 + 4096
+
+
+def _parentage_progeny_state(unit, plan, c, missing, budget):
+    """None where the rows of progeny c can be formed at this record, else why not: a refused shape, a candidate of its rows
+    without gametes (`missing`: those candidates), a launch beyond the budget."""
+    H = len(unit["locus"].haplotypes)
+    Kc = plan.ploidy[c]
+    if not _cross_evaluable(unit, Kc) or not all(_parentage_shape_ok(H, *shape) for shape in plan.launches[Kc]):
+        return "shape"
+    if any(s in missing for s in plan.used(c)):
+        return "candidate"
+    if budget is not None and any(_parentage_need(H, shape, len(plan.by_size.get(shape[1], ())) + 1) > budget for shape in plan.launches[Kc]):
+        return "budget"
+    return None
+
+
+def parentage_host(units, samples, ploidy_of, inbreeding_of, plan, gamete_error, backend, budget=None):
+    """The definition of the parentage evidence over a block, in float64 on `backend` (an object with the reference's
+    genotype_likelihoods; the oracle in the CPU tests).  For every record that needs the kernel and every progeny c of `plan`
+    (ParentagePlan), per row (P, Q) of plan.hypotheses[c]
+        lbf = log sum_{a, b} gam'_P[a] gam'_Q[b] exp(llk_c[rank(a + b)]) - log Z_pop,c                       (parentage_unit)
+    with gam' the candidate's gamete table under its calling prior at `gamete_error` (gamete_table), the population's for '.'
+    (population_gametes), and Z_pop,c the progeny's evidence under its own calling prior; ('.', '.') is exactly 0, and so is every
+    row of a progeny without reads.  Returns {(record index, progeny): float64 [rows] -- or None where the rows are not formed: a
+    candidate of the progeny's rows or the progeny itself without a finite genotype, a refused shape, a launch beyond `budget`
+    bytes}: the (record, progeny) is then left out of every row."""
+    e = float(gamete_error)
+    out = {}
+    for ri, unit in enumerate(units):
+        if not unit["needs_kernel"] or unit["invalid"] is not None:
+            continue
+        locus = unit["locus"]
+        H, f = len(locus.haplotypes), locus.frequencies
+        gam, missing = {}, set()
+        for s in plan.candidates:
+            K = plan.ploidy[s]
+            if not _cross_evaluable(unit, K):
+                missing.add(s)
+                continue
+            p, _ = _unit_posterior(_unit_llk(unit, s, K, backend), H, K, inbreeding_of(s), f)
+            if np.any(np.isnan(p)):
+                missing.add(s)
+            else:
+                gam[s] = gamete_table(p, H, K, f, e)
+        tables = {}
+        for c in plan.progeny:
+            rows = plan.hypotheses[c]
+            Kc = plan.ploidy[c]
+            if _parentage_progeny_state(unit, plan, c, missing, budget) is not None:
+                out[(ri, c)] = None
+                continue
+            if len(unit["reads"][c]["counts"]) == 0 or len(rows) == 1:
+                out[(ri, c)] = np.zeros(len(rows))
+                continue
+            llk_c = _unit_llk(unit, c, Kc, backend)
+            _, norm = _unit_posterior(llk_c, H, Kc, inbreeding_of(c), f)
+            if not np.isfinite(norm):
+                out[(ri, c)] = None
+                continue
+            for t in {t for shape in plan.launches[Kc] for t in shape}:
+                if t not in tables:   # (a candidate without gametes: a NaN row, in no row of this progeny)
+                    pop = population_gametes(H, t, f)
+                    tables[t] = np.stack([gam.get(s, np.full(len(pop), np.nan)) for s in plan.by_size.get(t, ())] + [pop])
+            z = {shape: parentage_unit(tables[shape[0]], tables[shape[1]], llk_c, H, *shape) for shape in plan.launches[Kc]}
+            lbf = np.zeros(len(rows))
+            for k, row in enumerate(rows[:-1]):
+                shape, i, j = plan.where(c, row)
+                lbf[k] = z[shape][i, j] - norm
+            out[(ri, c)] = lbf
+    return out
+
+
+def _parentage_device(units, samples, ploidy_of, inbreeding_of, plan, gamete_error, budget=None):
+    """parentage_host's result from the device.  Per shape group one likelihood pass (llks64 alone, cut by the free HBM): the
+    candidates' units go through the gamete launch (device.ExactParentage.gametes), the progeny's through the evidence launch for
+    Z_pop,c, their likelihoods kept on the device.  Then, per number of haplotypes, per progeny ploidy and per pair of gamete
+    sizes (t_a <= t_b) one table of each size -- the candidates' rows and the population's -- and as few parentage launches as the
+    budget allows (device_unit_budget over _parentage_need; `budget`: bytes, for the tests): all progeny of the ploidy and as many
+    records as fit.  A launch the library refuses is run again in smaller parts, first record by record, then progeny by progeny;
+    what is refused on its own is skipped (None), never an invalid record.  The results are read back after everything is
+    enqueued."""
+    from .device import ExactModelEvidence, ExactParentage
+
+    e = float(gamete_error)
+    out, llk, norm, gam, pending, flags = {}, {}, {}, {}, [], []
+    dev = ev = torch_isnan = None
+    for shape, group in _shape_groups(units, ploidy_of).items():
+        M, A, H, K = shape
+        for role in ("candidate", "progeny"):
+            who = plan.candidates if role == "candidate" else plan.progeny
+            members = [key for key in group if units[key[0]]["invalid"] is None and key[1] in who and _cross_evaluable(units[key[0]], K)
+                       and (role == "candidate" or len(units[key[0]]["reads"][key[1]]["counts"]) > 0)]
+            for flat in (True, False):
+                todo = [[key for key in members if (inbreeding_of(key[1]) is None) == flat]]
+                while todo:
+                    part = todo.pop(0)
+                    if not part:
+                        continue
+                    for chunk, batch in _estimate_group_batches(units, part, shape, lambda s: 0.0, 8, prior=False):
+                        recs = sorted({ri for ri, _ in chunk})
+                        row = {ri: i for i, ri in enumerate(recs)}
+                        try:
+                            if batch is None:
+                                raise NotImplementedError
+                            llks = batch.run_llks64()
+                            if dev is None:
+                                dev, ev = ExactParentage(), ExactModelEvidence()
+                                torch_isnan = dev.torch.isnan
+                            rows = [row[ri] for ri, _ in chunk]
+                            freqs = np.stack([units[ri]["locus"].frequencies for ri in recs])
+                            if role == "candidate":
+                                got = dev.gametes(llks, H, K, None if flat else [inbreeding_of(s) for _, s in chunk], rows, freqs, e)
+                                for i, key in enumerate(chunk):
+                                    gam[key] = got[i]
+                                flags.append((chunk, torch_isnan(got[:, 0])))
+                            else:
+                                grid = None if flat else np.array([[inbreeding_of(s)] for _, s in chunk], dtype=np.float64)
+                                got = ev.add_group(llks, H, K, grid, rows, freqs)
+                                table = llks.view(len(chunk), -1)
+                                for i, key in enumerate(chunk):
+                                    llk[key], norm[key] = table[i], (got, i)
+                        except NotImplementedError:
+                            if len(chunk) > 1:
+                                todo.extend([key] for key in chunk)   # (a refused chunk again unit by unit; one refused on its own stays out)
+    by_haps = {}
+    for ri, unit in enumerate(units):
+        if unit["needs_kernel"] and unit["invalid"] is None:
+            by_haps.setdefault(len(unit["locus"].haplotypes), []).append(ri)
+    if budget is None:
+        budget = device_unit_budget(1, most=1 << 62)
+    state = {}
+    for H, recs in by_haps.items():
+        for Kc, shapes in plan.launches.items():
+            progeny = [c for c in plan.progeny if plan.ploidy[c] == Kc and len(plan.hypotheses[c]) > 1]
+            live = []
+            for ri in recs:
+                missing = {s for s in plan.candidates if (ri, s) not in gam}
+                for c in progeny:
+                    why = _parentage_progeny_state(units[ri], plan, c, missing, budget)
+                    reads = len(units[ri]["reads"][c]["counts"]) > 0
+                    if why is None and reads and (ri, c) not in llk:
+                        why = "likelihoods"
+                    state[(ri, c)] = why
+                    if why is None and reads and ri not in live:
+                        live.append(ri)
+            if not live or not progeny:
+                continue
+            torch = dev.torch
+            tables = {}
+            freqs = np.stack([units[ri]["locus"].frequencies for ri in live])
+            for t in sorted({t for shape in shapes for t in shape}):
+                NA = dev._gametes(H, t)
+                nan = torch.full((NA,), float("nan"), dtype=torch.float64, device=dev.device)
+                cands = plan.by_size.get(t, [])
+                rows = torch.stack([torch.stack([gam.get((ri, s), nan) for s in cands]) for ri in live]) if cands else None
+                tables[t] = dev.table(rows, freqs, H, t)
+            zeros = torch.zeros(dev.cross._shape(H, Kc), dtype=torch.float64, device=dev.device)
+            for shape in shapes:
+                ta, tb = shape
+                need = _parentage_need(H, shape, int(tables[tb].shape[1]))
+                per_launch = int(budget // max(need * len(progeny), 1))
+                if per_launch >= 1:
+                    todo = [(part, progeny) for part in _blocks(list(range(len(live))), per_launch)]
+                else:
+                    todo = [([i], part) for i in range(len(live)) for part in _blocks(progeny, max(1, int(budget // need)))]
+                while todo:
+                    part, prog = todo.pop(0)
+                    on = [[1 if state[(live[i], c)] is None and (live[i], c) in llk else 0 for c in prog] for i in part]
+                    if not any(any(r) for r in on):
+                        continue
+                    try:
+                        stack = torch.stack([llk.get((live[i], c), zeros) for i in part for c in prog]).reshape(-1)
+                        got = dev.log_evidence(tables[ta][part].contiguous(), tables[tb][part].contiguous(), stack, H, ta, tb,
+                                               np.array(on, dtype=np.int32).reshape(len(part), len(prog)), workspace_limit=budget)
+                        pending.append(([live[i] for i in part], prog, shape, got))
+                    except NotImplementedError:
+                        if len(part) > 1:
+                            todo.extend(([i], prog) for i in part)
+                        elif len(prog) > 1:
+                            todo.extend((part, [c]) for c in prog)
+                        else:
+                            state[(live[part[0]], prog[0])] = "refused"
+    # a candidate without a finite genotype: a NaN row of its table
+    bad = {}
+    for chunk, isnan in flags:
+        for (ri, s), flag in zip(chunk, isnan.cpu().numpy()):
+            if flag:
+                bad.setdefault(ri, set()).add(s)
+    z = {}
+    for recs, prog, shape, got in pending:
+        host = got.cpu().numpy()
+        for i, ri in enumerate(recs):
+            for k, c in enumerate(prog):
+                z[(ri, c, shape)] = host[i, k]
+    host_norm = {}
+    for ri, unit in enumerate(units):
+        if not unit["needs_kernel"] or unit["invalid"] is not None:
+            continue
+        for c in plan.progeny:
+            rows = plan.hypotheses[c]
+            if len(rows) == 1:
+                out[(ri, c)] = None if _parentage_progeny_state(unit, plan, c, set(), budget) is not None else np.zeros(1)
+                continue
+            if state.get((ri, c), "shape") is not None or any(s in bad.get(ri, ()) for s in plan.used(c)):
+                out[(ri, c)] = None
+                continue
+            if len(unit["reads"][c]["counts"]) == 0:
+                out[(ri, c)] = np.zeros(len(rows))
+                continue
+            t, at = norm[(ri, c)]
+            if id(t) not in host_norm:
+                host_norm[id(t)] = (t, t.cpu().numpy())
+            ln = float(host_norm[id(t)][1][at, 0])
+            if not np.isfinite(ln) or any((ri, c, shape) not in z for shape in plan.launches[plan.ploidy[c]]):
+                out[(ri, c)] = None
+                continue
+            lbf = np.zeros(len(rows))
+            for k, row in enumerate(rows[:-1]):
+                shape, i, j = plan.where(c, row)
+                lbf[k] = z[(ri, c, shape)][i, j] - ln
+            out[(ri, c)] = lbf
+    return out
+
+
+class Parentage:
+    """The accumulator of `call-exact --parentage`: per progeny and hypothesis -- a pair of candidate parents, a candidate and an
+    unknown parent ('.'), or two unknown parents -- the sum over the records of the natural log Bayes factor of the closed-form
+    cross model of `--cross-calls` against the progeny's own calling prior (parentage_host), over the records `call-exact` sends
+    to the kernel.  Every row of a progeny is summed over the same records -- a (record, progeny) whose rows cannot all be formed is
+    left out of all of them and counted in SKIPPED --, so the rows compare: the table lists them best first, with DELTA the log
+    Bayes factor against the best.  A record with a single haplotype, and a progeny without reads at a record, add exactly 0 to
+    every row and are counted in RECORDS.  The candidates are called from their own reads alone and enter record by record as
+    independent plug-in posteriors: no selfings, no double reduction, no linkage between the records.
+
+    samples: the source's; candidates: sample names, in the order their pairs are listed in; progeny: sample names, or None for
+    every sample that is not a candidate (a sample may be both); gamete_error: one value in [0, 1] for every candidate; top: the
+    rows kept per progeny (0: all); frequency_source: as ModelEvidence; budget: the device bytes a launch may take (None: a
+    share of the free memory)."""
+
+    HEADER = ("PROGENY", "PARENT_1", "PARENT_2", "RECORDS", "SKIPPED", "LOG_BF", "DELTA", "RANK")
+
+    def __init__(self, samples, candidates, progeny=None, gamete_error=0.01, top=0, frequency_source="flat",
+                 program="mchap_amd call-exact", budget=None):
+        self.samples = list(samples)
+        self.candidates = list(candidates)
+        self.progeny = None if progeny is None else list(progeny)
+        self.gamete_error, self.top = float(gamete_error), int(top)
+        if not 0.0 <= self.gamete_error <= 1.0:   # (False for NaN too)
+            raise ValueError("parentage: the gamete error lies in [0, 1]")
+        if self.top < 0:
+            raise ValueError("parentage: the number of rows kept per progeny is 0 (all) or more")
+        self.frequency_source, self.program, self.budget = frequency_source, program, budget
+        self.plan = None
+        self.sums = self.records = self.skipped = None
+        self.records_seen = 0
+
+    def resolve(self, ploidy_of):
+        """The run's ParentagePlan, formed and checked once; a progeny that no hypothesis but ('.', '.') fits is named on stderr."""
+        import sys
+
+        plan = ParentagePlan(self.samples, self.candidates, self.progeny, ploidy_of)
+        if self.plan is None:
+            self.plan = plan
+            for c in plan.progeny:
+                if len(plan.hypotheses[c]) == 1:
+                    print("WARNING: parentage: no candidate fits progeny %s of ploidy %d: its one row is the unknown pair" % (c, plan.ploidy[c]),
+                          file=sys.stderr)
+            self.sums = {c: np.zeros(len(plan.hypotheses[c])) for c in plan.progeny}
+            self.records = {c: 0 for c in plan.progeny}
+            self.skipped = {c: 0 for c in plan.progeny}
+        elif plan.ploidy != self.plan.ploidy:
+            raise ValueError("parentage: the samples' ploidy changed between blocks")
+        return self.plan
+
+    def add_block(self, units, ploidy_of, inbreeding_of, backend=None):
+        """The records of a block (what _exact_units returned, after the frequency estimate where there is one): every (record,
+        progeny) adds its rows to the progeny's sums, in record order, in float64 on the host.  backend: the definition on that
+        object (parentage_host); None = the device."""
+        plan = self.resolve(ploidy_of)
+        self.records_seen += len(units)
+        if backend is not None:
+            got = parentage_host(units, self.samples, ploidy_of, inbreeding_of, plan, self.gamete_error, backend, self.budget)
+        else:
+            got = _parentage_device(units, self.samples, ploidy_of, inbreeding_of, plan, self.gamete_error, self.budget)
+        for ri, unit in enumerate(units):
+            for c in plan.progeny:
+                if (ri, c) in got:
+                    lbf = got[(ri, c)]
+                    if lbf is None:
+                        self.skipped[c] += 1
+                        continue
+                    self.sums[c] = self.sums[c] + lbf
+                elif unit["invalid"] is not None or len(unit["locus"].haplotypes) != 1:
+                    continue   # (a record the run does not call; a single haplotype: one genotype under either prior, exactly 0)
+                self.records[c] += 1
+        return got
+
+    def table(self):
+        """The rows, progeny in sample order, within a progeny by LOG_BF descending (ties in hypothesis order), the first `top` of
+        each where top > 0: dicts of HEADER's names in lower case."""
+        rows = []
+        for c in self.plan.progeny if self.plan is not None else []:
+            sums = self.sums[c]
+            order = sorted(range(len(sums)), key=lambda k: -sums[k])   # (stable: ties stay in hypothesis order)
+            best = sums[order[0]]
+            for rank, k in enumerate(order[:self.top] if self.top else order):
+                p, q = self.plan.hypotheses[c][k]
+                rows.append(dict(progeny=c, parent_1=p, parent_2=q, records=self.records[c], skipped=self.skipped[c],
+                                 log_bf=float(sums[k]) + 0.0, delta=0.0 if sums[k] == best else float(sums[k] - best), rank=rank + 1))
+        return rows
+
+    def text(self):
+        lines = ["# %s parentage; frequencies: %s; gamete error: %g; records: %d"
+                 % (self.program, self.frequency_source, self.gamete_error, self.records_seen), "\t".join(self.HEADER)]
+        for r in self.table():
+            lines.append("\t".join([r["progeny"], r["parent_1"], r["parent_2"], "%d" % r["records"], "%d" % r["skipped"],
+                                    "%.6f" % r["log_bf"], "%.6f" % r["delta"], "%d" % r["rank"]]))
+        return "\n".join(lines) + "\n"
+
+    def write(self, path):
+        with open(path, "w") as fh:
+            fh.write(self.text())
+
+
 def _per_sample(value, samples):
     """A scalar, or a {sample: value} mapping (the reference's per-sample ploidy / inbreeding files), as a function."""
     if isinstance(value, dict):
@@ -1970,7 +2432,7 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
                prior_frequencies_tag=None, inbreeding=None, calling=None, filter_input_haplotypes=None, read_kw=None,
                records_per_block=4096, shard=None, block_path=None, estimate_frequencies=None, estimate_tolerance=1e-6,
                estimate_path=None, model_evidence=None, snv_calls=None, allele_depths=None, cross_calls=None,
-               family_calls=None):
+               family_calls=None, parentage=None):
     """`mchap call-exact` over a VCF of known haplotypes: yields one VCF record line per input record (no header).
     sample_bams: ordered mapping sample name -> BAM path (or pool -> [(sample, path)], or a ReadSource); ploidy /
     inbreeding: a value or {sample: value}.  The records are processed in blocks: the (record x sample) units of a block
@@ -2014,7 +2476,10 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
 
     family_calls: a FamilyCalls over the source's samples; every block's own lines are handed to it likewise, and it adds them with
     FGT, FGPM and FLBF: the parents and the progeny of its cross called jointly (the record lines do not depend on it).  Not with
-    `shard`."""
+    `shard`.
+
+    parentage: a Parentage over the source's samples; every block adds to it, after the frequency estimate -- so the estimated
+    prior is the one used -- (the record lines do not depend on it).  Not with `shard`: the sums of several ranks are not combined."""
     from .vcfheader import report_fields
 
     if model_evidence is not None and shard is not None:
@@ -2027,9 +2492,13 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
         raise ValueError("cross_calls runs as a single process: the file is not gathered from several ranks (shard)")
     if family_calls is not None and shard is not None:
         raise ValueError("family_calls runs as a single process: the file is not gathered from several ranks (shard)")
+    if parentage is not None and shard is not None:
+        raise ValueError("parentage runs as a single process: it does not combine the sums of several ranks (shard)")
     source = _source(sample_bams, base_error_rate, use_base_phred_scores, read_kw)
     block_path = _call_block_path(block_path, source)
     samples = source.samples
+    if parentage is not None and list(parentage.samples) != list(samples):
+        raise ValueError("parentage: its samples are not the source's")
     if family_calls is not None and list(family_calls.samples) != list(samples):
         raise ValueError("family_calls: its samples are not the source's")
     if allele_depths is not None and list(allele_depths.samples) != list(samples):
@@ -2053,6 +2522,8 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
                                        estimate_path)
         if model_evidence is not None:
             model_evidence.add_block(units, ploidy_of, inbreeding_of, calling)
+        if parentage is not None:
+            parentage.add_block(units, ploidy_of, inbreeding_of, calling)
         results = _run_exact_groups(units, ploidy_of, inbreeding_of, full, calling)
         lines = []
         for ri, unit in enumerate(units):

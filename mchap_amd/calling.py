@@ -273,6 +273,26 @@ def cross_genotype_posteriors(llks, log_cross_prior):
     return dev.posteriors(llk, G, 1, lx, [0], full=True)[4][0].cpu().numpy()
 
 
+def parentage_log_evidence(gametes_a, gametes_b, llks, n_alleles, t_a, t_b):
+    """The cross evidence of progeny under every pair of rows of two gamete tables (not a reference function; the definition:
+    application.parentage_unit): gametes_a [n_a, C(H + t_a - 1, t_a)] and gametes_b [n_b, C(H + t_b - 1, t_b)] distributions over the
+    gametes of t_a and t_b haplotypes out of n_alleles (VCF order), llks [n, G_c] -- or [G_c] for one progeny -- the log likelihoods
+    of progeny of ploidy t_a + t_b.  Returns float64 [n, n_a, n_b] (or [n_a, n_b]):
+        log sum_a gametes_a[i][a] sum_b gametes_b[j][b] exp(llks[c][rank(a + b)])."""
+    import torch
+
+    from .device import ExactParentage
+
+    dev = ExactParentage()
+    llk = np.ascontiguousarray(llks, dtype=np.float64)
+    one = llk.ndim == 1
+    tables = [torch.from_numpy(np.ascontiguousarray(np.atleast_2d(np.asarray(g, dtype=np.float64)))[None]).to(dev.device)
+              for g in (gametes_a, gametes_b)]
+    got = dev.log_evidence(tables[0], tables[1], torch.from_numpy(llk.reshape(-1)).to(dev.device), int(n_alleles), int(t_a), int(t_b))
+    out = got.cpu().numpy()[0]
+    return out[0] if one else out
+
+
 def family_genotype_posteriors(llks_p, ploidy_p, llks_q, ploidy_q, llks_progeny, n_alleles, log_prior_p=None, log_prior_q=None,
                                gamete_error=(0, 0), frequencies=None):
     """The joint call of one nuclear family (not a reference function; the definition: application.family_unit): parents with log

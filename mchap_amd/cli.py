@@ -18,7 +18,9 @@ SNV-level VCF `atomize` would make of the run's output with GQ, DS and ACP from 
 (application.SnvCalls), and `call-exact --allele-depths FILE`, which writes the run's VCF again with ADP, the posterior expected read
 depth of every allele (application.AlleleDepths), and `call-exact --cross-calls FILE --cross-parents P Q`, which writes the run's VCF
 again with the progeny of that cross called under their parents' cross prior (application.CrossCalls), and `call-exact --family-calls
-FILE --cross-parents P Q`, which writes it with the parents and the progeny called jointly (application.FamilyCalls).  `atomize --haplotypes FILE` is host only (mchap_amd/atomize.py)."""
+FILE --cross-parents P Q`, which writes it with the parents and the progeny called jointly (application.FamilyCalls), and `call-exact
+--parentage FILE --parentage-candidates A B ... [--parentage-progeny C ...] [--parentage-gamete-error E] [--parentage-top N]`, which
+writes a table that ranks every pair of candidate parents per progeny (application.Parentage).  `atomize --haplotypes FILE` is host only (mchap_amd/atomize.py)."""
 import argparse
 import sys
 
@@ -185,6 +187,19 @@ def build_parser(program):
             p.add_argument("--gamete-error", type=float, nargs="+", default=None, metavar="E",
                            help="(not a reference flag) with --cross-calls: the probability that a gamete is drawn from the population "
                                 "and not from its parent, one value or one for P and one for Q, in [0, 1] (default: 0.01)")
+            p.add_argument("--parentage", type=str, nargs=1, default=[None], metavar="FILE",
+                           help="(not a reference flag) write to FILE, when the run ends, a table that ranks, for every progeny, every "
+                                "pair of the candidate parents --parentage-candidates -- and every candidate with an unknown parent -- by "
+                                "the log Bayes factor of the cross model of --cross-calls against unrelated, summed over the records")
+            p.add_argument("--parentage-candidates", type=str, nargs="+", default=None, metavar="SAMPLE",
+                           help="(not a reference flag) with --parentage: the candidate parents, by sample name, each of even ploidy")
+            p.add_argument("--parentage-progeny", type=str, nargs="+", default=None, metavar="SAMPLE",
+                           help="(not a reference flag) with --parentage: the progeny (default: every sample that is not a candidate)")
+            p.add_argument("--parentage-gamete-error", type=float, nargs=1, default=[None], metavar="E",
+                           help="(not a reference flag) with --parentage: the probability that a gamete is drawn from the population and "
+                                "not from its parent, one value in [0, 1] for every candidate (default: 0.01)")
+            p.add_argument("--parentage-top", type=int, nargs=1, default=[None], metavar="N",
+                           help="(not a reference flag) with --parentage: keep the first N rows of every progeny (default 0: all)")
             p.add_argument("--snv-report", type=str, nargs="+", default=None, metavar="FIELD", choices=["GP"],
                            help="(not a reference flag) with --snv-calls: GP adds the SNV genotype posteriors as a sixth FORMAT field")
     p.add_argument("--report", type=str, nargs="*", default=[],
@@ -251,7 +266,7 @@ def run(argv, out=None):
                                     read_group_field=id_field, mapping_quality=args.mapping_quality[0],
                                     skip_duplicates=args.skip_duplicates, skip_qcfail=args.skip_qcfail,
                                     skip_supplementary=args.skip_supplementary, workers=args.cores[0])
-    seed = evidence = snv_calls = allele_depths = cross_calls = family_calls = header = None
+    seed = evidence = snv_calls = allele_depths = cross_calls = family_calls = parentage = header = None
     block_path = BLOCK_PATHS[args.block_path]
     if program == "assemble":
         if args.targets[0] is not None and args.region[0] is not None:
@@ -296,12 +311,13 @@ def run(argv, out=None):
             allele_depths = allele_depths_settings(args, samples, world, header)
             cross_calls = cross_calls_settings(args, samples, ploidy, world, header)
             family_calls = family_calls_settings(args, samples, ploidy, world, header)
+            parentage = parentage_settings(args, samples, ploidy, inbreeding, tag, estimate, world)
             records = application.call_exact(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
                                              inbreeding=inbreeding, filter_input_haplotypes=args.filter_input_haplotypes[0], shard=shard,
                                              block_path=block_path, estimate_frequencies=estimate,
                                              estimate_tolerance=1e-6 if args.estimate_tolerance[0] is None else args.estimate_tolerance[0],
                                              model_evidence=evidence, snv_calls=snv_calls, allele_depths=allele_depths,
-                                             cross_calls=cross_calls, family_calls=family_calls)
+                                             cross_calls=cross_calls, family_calls=family_calls, parentage=parentage)
         else:
             seed = args.mcmc_seed[0]
             records = application.call(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
@@ -340,6 +356,8 @@ def run(argv, out=None):
         cross_calls.write(args.cross_calls[0])
     if family_calls is not None:
         family_calls.write(args.family_calls[0])
+    if parentage is not None:
+        parentage.write(args.parentage[0])
     return n
 
 
@@ -352,10 +370,12 @@ ALLELE_DEPTH_FLAGS = ("--allele-depths",)
 CROSS_FLAGS = ("--cross-calls", "--cross-parents", "--cross-progeny", "--gamete-error")
 # ... and the flag of the family-calls file, which takes its cross from the three above
 FAMILY_FLAGS = ("--family-calls",)
+# ... and the flags of the parentage table
+PARENTAGE_FLAGS = ("--parentage", "--parentage-candidates", "--parentage-progeny", "--parentage-gamete-error", "--parentage-top")
 
 
 def _header_argv(argv, options):
-    """The command line as the VCF header states it: without the model-evidence, SNV-file, allele-depths, cross-calls and family-calls flags and their values -- the VCF, header included,
+    """The command line as the VCF header states it: without the model-evidence, SNV-file, allele-depths, cross-calls, family-calls and parentage flags and their values -- the VCF, header included,
     is byte for byte what the run writes without them.  options: the parser's option strings; a flag is resolved as argparse
     resolves it (the exact name, else the one option it is a prefix of), so an abbreviated flag is taken out too."""
     out, skipping = [], False
@@ -363,7 +383,7 @@ def _header_argv(argv, options):
         if a.startswith("--"):
             name = a.split("=", 1)[0]
             full = [name] if name in options else [o for o in options if o.startswith(name)]
-            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS + SNV_FLAGS + ALLELE_DEPTH_FLAGS + CROSS_FLAGS + FAMILY_FLAGS
+            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS + SNV_FLAGS + ALLELE_DEPTH_FLAGS + CROSS_FLAGS + FAMILY_FLAGS + PARENTAGE_FLAGS
         if not skipping:
             out.append(a)
     return out
@@ -461,6 +481,34 @@ def family_calls_settings(args, samples, ploidy, world, header_lines):
     calls = application.FamilyCalls(samples, args.cross_parents, args.cross_progeny, error, header_lines)
     calls.cross.resolve(list(samples), application._per_sample(ploidy, samples))
     return calls
+
+
+def parentage_settings(args, samples, ploidy, inbreeding, tag, estimate, world):
+    """The --parentage / --parentage-* flags of call-exact -> an application.Parentage, or None without --parentage (any
+    --parentage-* flag is then an error).  The hypotheses are checked here, before any work: the sample names, none twice, every
+    candidate of even ploidy, the gamete error in [0, 1], N >= 0."""
+    from . import application
+
+    if args.parentage[0] is None:
+        for flag, value in (("--parentage-candidates", args.parentage_candidates), ("--parentage-progeny", args.parentage_progeny),
+                            ("--parentage-gamete-error", args.parentage_gamete_error[0]), ("--parentage-top", args.parentage_top[0])):
+            if value is not None:
+                raise ValueError("%s needs --parentage" % flag)
+        return None
+    if args.parentage_candidates is None:
+        raise ValueError("--parentage needs --parentage-candidates SAMPLE [SAMPLE ...]")
+    if world > 1:
+        raise ValueError("--parentage runs as a single process: it does not combine the sums of several ranks (WORLD_SIZE > 1)")
+    error = 0.01 if args.parentage_gamete_error[0] is None else args.parentage_gamete_error[0]
+    if not 0.0 <= error <= 1.0:   # (False for NaN too)
+        raise ValueError("--parentage-gamete-error: one value in [0, 1]")
+    top = 0 if args.parentage_top[0] is None else args.parentage_top[0]
+    if top < 0:
+        raise ValueError("--parentage-top: N >= 0")
+    source = "estimated" if estimate is not None else ("flat" if (tag is None or inbreeding is None) else "tag %s" % tag)
+    table = application.Parentage(samples, args.parentage_candidates, args.parentage_progeny, error, top, frequency_source=source)
+    table.resolve(application._per_sample(ploidy, samples))
+    return table
 
 
 def _run_atomize(argv, args, out):

@@ -990,6 +990,113 @@ class ExactCross:
         return (log_z, mode, prob, norm, post) if full else (log_z, mode, prob, norm)
 
 
+class ExactParentage:
+    """Candidate parent pairs per progeny for exact-caller units whose likelihoods are resident on the device
+    (mchap_exact_parentage_device): the cross evidence of every progeny of a record under every pair of rows of two gamete tables.
+    The rows are what ExactCross.gametes returns for the candidates (`gametes` here: one gamete error for all), and the
+    population's row of the unknown parent (`population`).  The definition: application.parentage_unit."""
+
+    TMAX = 7   # the largest gamete size (exact_parentage_kernel.hpp PARENTAGE_TMAX)
+
+    def __init__(self, device=None):
+        self.torch = _torch()
+        self.device = _device(self.torch, device)
+        self.cross = ExactCross(self.device)
+        self.launches = 0      # calls enqueued (the gamete launches are counted in self.cross)
+
+    _tensor = ExactModelEvidence._tensor
+
+    @classmethod
+    def _gametes(cls, H, t):
+        if t < 1 or t > cls.TMAX or comb(H + t - 1, t) >= 1 << 62:
+            raise NotImplementedError("mchap_hip: gametes of %d haplotypes over %d are beyond this build's parentage kernel" % (t, H))
+        return comb(H + t - 1, t)
+
+    def gametes(self, llks64, n_haps, ploidy, inbreeding, unit_row, freqs, gamete_error):
+        """The candidates' gamete rows [U, C(H + t - 1, t)]: ExactCross.gametes at one gamete error in [0, 1] for every unit -- checked
+        there, on the host copy."""
+        return self.cross.gametes(llks64, n_haps, ploidy, inbreeding, unit_row, freqs, float(gamete_error))
+
+    def population(self, freqs, n_haps, t, out=None):
+        """Mult(a; t, f) of every gamete of t haplotypes for the records' frequencies freqs [R, stride >= n_haps] -- the unknown
+        parent's row, what the gamete launch returns at a gamete error of 1 --, formed on the device: a float64 tensor [R, NA], or
+        written into out [R, NA], a view whose rows may be strided (a row of a table)."""
+        torch = self.torch
+        H, t = int(n_haps), int(t)
+        NA = self._gametes(H, t)
+        d_fr = self._tensor(freqs, torch.float64, np.float64)
+        assert d_fr.dim() == 2 and int(d_fr.shape[1]) >= H
+        R = int(d_fr.shape[0])
+        if out is None:
+            out = torch.empty((R, NA), dtype=torch.float64, device=self.device)
+        assert out.dtype == torch.float64 and tuple(out.shape) == (R, NA) and (R == 0 or (out.stride(1) == 1 and out.stride(0) >= NA))
+        if R:
+            _lib.check(_lib.lib().mchap_exact_parentage_population_device(
+                R, _ptr(d_fr), int(d_fr.shape[1]), H, t, _ptr(out), C.c_int64(int(out.stride(0)) if R > 1 else NA),
+                C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            self.launches += 1
+        return out
+
+    def table(self, rows, freqs, n_haps, t):
+        """The table [R, n + 1, NA] of a gamete size: rows [R, n, NA] the candidates' gamete rows (a float64 tensor on the device,
+        n may be 0, or None), and the population's row of every record last."""
+        torch = self.torch
+        H, t = int(n_haps), int(t)
+        NA = self._gametes(H, t)
+        d_fr = self._tensor(freqs, torch.float64, np.float64)
+        R = int(d_fr.shape[0])
+        n = 0 if rows is None else int(rows.shape[1])
+        out = torch.empty((R, n + 1, NA), dtype=torch.float64, device=self.device)
+        if n:
+            assert rows.dtype == torch.float64 and tuple(rows.shape) == (R, n, NA)
+            out[:, :n] = rows
+        self.population(d_fr, H, t, out[:, n])
+        return out
+
+    @staticmethod
+    def workspace_bytes(n_records, n_progeny, n_a, n_b, n_haps, t_a, t_b):
+        """The bytes of workspace a call needs, or -1 for a shape the kernels refuse."""
+        return int(_lib.lib().mchap_exact_parentage_workspace_bytes(int(n_records), int(n_progeny), int(n_a), int(n_b), int(n_haps),
+                                                                    int(t_a), int(t_b)))
+
+    def log_evidence(self, gametes_a, gametes_b, llks_c, n_haps, t_a, t_b, progeny_reads=None, workspace_limit=None):
+        """The records of one shape, enqueued on torch's current stream: gametes_a [R, n_a, NA], gametes_b [R, n_b, NB] float64
+        tensors on the device (they may be one tensor), llks_c [R * C * G_c] the progeny's likelihoods, progeny_reads [R, C] of
+        0 / 1 (None: every progeny has reads).  workspace_limit: the bytes the caller offers (None: what the device has free); a
+        workspace beyond it, or a shape the library refuses: NotImplementedError.  Returns log_z [R, C, n_a, n_b] on the device."""
+        torch, dev = self.torch, self.device
+        H, ta, tb = int(n_haps), int(t_a), int(t_b)
+        NA, NB = self._gametes(H, ta), self._gametes(H, tb)
+        GC = ExactCross._shape(H, ta + tb)
+        for g, N in ((gametes_a, NA), (gametes_b, NB)):
+            assert g.dtype == torch.float64 and g.is_contiguous() and g.dim() == 3 and int(g.shape[2]) == N and int(g.shape[1]) >= 1
+        R, n_a, n_b = int(gametes_a.shape[0]), int(gametes_a.shape[1]), int(gametes_b.shape[1])
+        assert int(gametes_b.shape[0]) == R
+        assert llks_c.dtype == torch.float64 and llks_c.is_contiguous() and (R == 0 or llks_c.numel() % (R * GC) == 0)
+        n = llks_c.numel() // (R * GC) if R else 0
+        d_reads = None
+        if progeny_reads is not None:
+            reads = np.ascontiguousarray(progeny_reads, dtype=np.int32)
+            assert reads.shape == (R, n)
+            d_reads = torch.from_numpy(reads).to(dev)
+        out = torch.empty((R, n, n_a, n_b), dtype=torch.float64, device=dev)
+        if R == 0 or n == 0:
+            return out
+        wsb = self.workspace_bytes(R, n, n_a, n_b, H, ta, tb)
+        limit = workspace_limit
+        if limit is None:
+            limit, _ = torch.cuda.mem_get_info()
+        if wsb < 0 or wsb > limit:
+            raise NotImplementedError("mchap_hip: parentage of %d records x %d progeny x %d columns over %d haplotypes: the shape is "
+                                      "refused, or its workspace does not fit the device" % (R, n, n_b, H))
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().mchap_exact_parentage_device(
+            R, n, n_a, n_b, _ptr(gametes_a), _ptr(gametes_b), _ptr(llks_c), _ptr(d_reads), H, ta, tb, _ptr(out), _ptr(ws),
+            C.c_int64(wsb), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        self.launches += 1
+        return out
+
+
 class ExactFamily:
     """The parents and the progeny of one cross called jointly for exact-caller units whose likelihoods are resident on the device
     (mchap_exact_family_device): per record the exact joint posterior of the two parents and all progeny, its marginals and every
