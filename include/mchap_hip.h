@@ -545,6 +545,34 @@ int mchap_exact_parentage_device(int n_records, int n_progeny, int n_a, int n_b,
 int mchap_exact_parentage_population_device(int n_records, const double *frequencies, int stride, int n_haps, int t, double *rows,
                                             int64_t row_pitch, void *stream);
 
+/* Sample pairs by shared-genotype evidence (call-exact --identity): per record, for every pair (i, j) of n_samples samples of one
+ * ploidy under one calling prior pi -- `inbreeding`: a HOST pointer to the one F in [0, 1) of the launch, read during the call, or
+ * NULL for the flat prior; frequencies [n_records][stride], a device array, record r's row r (not read under the flat prior) --,
+ * over llks64 [n_records][n_samples][G] as mchap_exact_call_batch_device leaves them and log_norm [n_records][n_samples], every
+ * sample's model evidence under that prior (mchap_exact_evidence_device, one grid point):
+ *   a_s[g]    = exp(llk_s[g] + log pi(g) / 2 - m_s),  m_s = max_g (llk_s[g] + log pi(g) / 2)       once per (record, sample)
+ *   S_ij      = sum_g a_i[g] a_j[g]                         a sum below 1e-290 counts as 0
+ *   lbf[r][i][j] = log((1 - error) r_ij + error),  log r_ij = log S_ij + (m_i - log_norm_i) + (m_j - log_norm_j)
+ * the log Bayes factor of "one genotype read twice" against two independent draws from pi, error in [0, 1] the probability that the
+ * genotypes are independent at this record all the same.  Both triangles are written, with equal bits, and the diagonal is NaN.
+ * reads [n_records][n_samples] (or NULL: every sample has reads): the read weight of a (record, sample), 0 meaning no reads -- its
+ * likelihoods are not read and its pairs are exactly 0.  A sample without a finite llk + log pi, or with a NaN, has NaN in its
+ * row and column (also against a sample without reads).  S_ij = 0 gives log(error), -inf at error = 0.
+ * The product is register-tiled (tiles of 64 x 64 pairs on or above the diagonal, 4 x 4 accumulators per thread) over chunks of the
+ * genotype axis whose boundaries depend on G alone; a combine launch adds the chunks in order.  No atomics: equal inputs give equal
+ * bits whatever the place of a record in the call and the number and order of the samples.  `workspace`:
+ * mchap_exact_identity_workspace_bytes (log pi / 2 per record, the rows a, the chunks' partial sums); -1, with the call itself
+ * MCHAP_ERR_LIMIT, for a ploidy beyond MCHAP_MAX_PLOIDY_DENOVO, 2^62 genotypes or more, or arrays of 2^61 bytes; with a prior the call
+ * is MCHAP_ERR_LIMIT too where its tables exceed the LDS (mchap_exact_evidence_chunk = 0: the evidence launch refuses the shape as
+ * well).  A workspace smaller than asked is MCHAP_ERR_LIMIT.  phases: 3 = the whole call; 1 = the launches that form log pi / 2 and
+ * the rows a in the workspace, and no more; 2 = the product and combine launches over the rows a call with phases = 1 left in the
+ * same workspace (same arguments) -- for a caller that times the two, or changes `error` alone.  Enqueue on `stream`, no
+ * synchronisation. */
+int64_t mchap_exact_identity_workspace_bytes(int n_records, int n_samples, int n_haps, int ploidy);
+int mchap_exact_identity_device(int n_records, int n_samples, const double *llks64, int n_haps, int ploidy, const double *inbreeding,
+                                const double *frequencies, int stride, const double *log_norm, double error, const int32_t *reads,
+                                double *lbf, int phases, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Summaries of given posterior arrays [U][G] (calling.exact.posterior_allele_frequencies 332-369, the sum of
  * alternate_dosage_posteriors 372-407 for the array's mode): device pointers, any output may be NULL. */
 int mchap_exact_posterior_summaries_batch_device(int n_units, const double *posteriors, int64_t n_genotypes, int ploidy,

@@ -2357,6 +2357,339 @@ class Parentage:
             fh.write(self.text())
 
 
+# ---------------------------------------------------------------------------------------------------------
+# call-exact --identity: every pair of samples ranked by the evidence that they are one individual
+# ---------------------------------------------------------------------------------------------------------
+IDENTITY_TINY = 1e-290      # a scaled sum below this counts as 0 (exact_identity_kernel.hpp IDENTITY_TINY)
+IDENTITY_CHUNK = 2048       # the genotypes of a chunk of the product, at least, and the most chunks (exact_identity_kernel.hpp)
+IDENTITY_MAXCHUNK = 16
+
+
+def identity_term(S, c, error):
+    """log((1 - e) r + e) with log r = log S + c, elementwise in float64, as the kernel forms it (exact_identity_kernel.hpp
+    identity_term): a scaled sum S below IDENTITY_TINY counts as 0; e = 0 is log r itself (-inf at S = 0), e = 1 is exactly 0,
+    log r above 700 is log r + log(1 - e)."""
+    e = float(error)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        S = np.asarray(S, dtype=np.float64)
+        S = np.where(S < IDENTITY_TINY, 0.0, S)
+        lr = np.log(S) + c
+        if e == 0.0:
+            return lr
+        if e == 1.0:
+            return np.where(np.isnan(lr), np.nan, 0.0)
+        return np.where(lr > 700.0, lr + np.log1p(-e), np.log((1.0 - e) * np.exp(np.minimum(lr, 700.0)) + e))
+
+
+def identity_unit(llks, log_prior, error, reads=None):
+    """The definition of the identity evidence of one record, in float64: for the log likelihoods llks [n, G] of n samples of one
+    ploidy and their normalised log calling prior log_prior [G], float64 [n, n],
+        lbf[i][j] = log((1 - e) r_ij + e),  r_ij = sum_g pi(g) L_i(g) L_j(g) / (Z_i Z_j) = sum_g post_i(g) post_j(g) / pi(g),
+    the log Bayes factor of "one genotype, read twice" against two independent draws from the prior, e the probability that the
+    two genotypes are independent at this record all the same.  In the kernel's form (exact_identity_kernel.hpp):
+    a_s(g) = exp(llk_s(g) + log pi(g) / 2 - m_s) with m_s the largest exponent, S_ij = sum_g a_i(g) a_j(g) -- a sum below 1e-290
+    counts as 0: the pair disagrees by more than about 660 nats at the samples' own best genotypes --, log r_ij = log S_ij +
+    (m_i - log Z_i) + (m_j - log Z_j) (identity_term).  The diagonal is NaN; n may be 1.  reads [n] (None: every sample has
+    reads): 0 for a sample without reads, whose pairs are exactly 0 -- r = 1 by definition, its likelihoods are not looked at.  A
+    sample with reads without a finite llk + log pi, or with a NaN, has NaN in its row and column: the pair is not formed.
+    Held to a long-double restatement in plain loops (tests/identity_reference.py): largest difference 1.33e-15 over the shapes of
+    tests/test_identity_reference.py."""
+    A = np.atleast_2d(np.asarray(llks, dtype=np.float64))
+    lp = np.asarray(log_prior, dtype=np.float64)
+    n = len(A)
+    has = np.ones(n, dtype=bool) if reads is None else np.asarray(reads) != 0
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        w = A + 0.5 * lp
+        m = np.where(np.any(np.isnan(w), axis=1), np.nan, np.max(w, axis=1))
+        a = np.exp(w - m[:, None])
+        a[~has] = 0.0
+        log_z = np.array([_logsumexp(row) if not np.any(np.isnan(row)) else np.nan for row in A + lp])
+        bad = has & ~(np.isfinite(m) & np.isfinite(log_z))
+        c = np.where(has & ~bad, m - log_z, 0.0)
+        a[bad] = 0.0
+        lbf = identity_term(a @ a.T, c[:, None] + c[None, :], error)
+    lbf[~has, :] = 0.0
+    lbf[:, ~has] = 0.0
+    lbf[bad, :] = np.nan
+    lbf[:, bad] = np.nan
+    lbf[np.arange(n), np.arange(n)] = np.nan
+    return lbf
+
+
+class IdentityPlan:
+    """The pairs of an identity run: `names` (None: every sample), checked against the run's samples; classes: the chosen samples
+    in sample order, grouped by (ploidy, F) -- F None: the flat prior --, the groups in order of first appearance; a pair is
+    compared where both samples are of one class.  pairs: the compared (i, j), i before j in sample order, in pair order;
+    not_compared: the number of pairs across classes."""
+
+    def __init__(self, samples, names, ploidy_of, inbreeding_of):
+        samples = list(samples)
+        names = samples if names is None else list(names)
+        for s in names:
+            if s not in samples:
+                raise ValueError("identity: sample %r is not a sample of this run" % s)
+            if names.count(s) > 1:
+                raise ValueError("identity: sample %r is named more than once" % s)
+        if len(names) < 2:
+            raise ValueError("identity: at least two samples are needed")
+        self.samples = [s for s in samples if s in names]   # (sample order)
+        self.key = {}
+        for s in self.samples:
+            F = inbreeding_of(s)
+            self.key[s] = (int(ploidy_of(s)), None if F is None else float(F))
+        self.classes = {}
+        for s in self.samples:
+            self.classes.setdefault(self.key[s], []).append(s)
+        self.pairs = [(p, q) for i, p in enumerate(self.samples) for q in self.samples[i + 1:] if self.key[p] == self.key[q]]
+        self.not_compared = len(self.samples) * (len(self.samples) - 1) // 2 - len(self.pairs)
+
+    def compared(self):
+        """The classes that hold a pair: [((ploidy, F), [samples])]."""
+        return [(key, members) for key, members in self.classes.items() if len(members) >= 2]
+
+
+def _identity_need(H, K, n):
+    """Device bytes of one record of an identity launch over n samples: its likelihoods stacked for the launch, the rows a, the
+    half log prior, the chunks' partial sums and the result."""
+    from math import comb
+
+    G = comb(H + K - 1, K)
+    nchunk = max(1, min(IDENTITY_MAXCHUNK, -(-G // IDENTITY_CHUNK)))
+    return (2 * n * G + G + (nchunk + 1) * n * n + 2 * n) * 8 + 4096
+
+
+def _identity_class_state(unit, key, n, budget):
+    """None where the pairs of a class can be formed at this record, else why not: a shape the library refuses (the ploidy, 2^62
+    genotypes, the prior tables beyond the LDS as for the model evidence), the class's arrays beyond the budget."""
+    K, F = key
+    H = len(unit["locus"].haplotypes)
+    if not _cross_evaluable(unit, K) or not _evidence_evaluable(H, [key]):
+        return "shape"
+    if budget is not None and _identity_need(H, K, n) > budget:
+        return "budget"
+    return None
+
+
+def identity_host(units, samples, ploidy_of, inbreeding_of, plan, error, backend, budget=None):
+    """The definition of the identity evidence over a block, in float64 on `backend` (an object with the reference's
+    genotype_likelihoods; the oracle in the CPU tests).  For every record that needs the kernel and every class of `plan`
+    (IdentityPlan) that holds a pair: identity_unit over the class's samples under their calling prior at the record's
+    frequencies.  Returns {(record index, class key): float64 [n, n] -- NaN where the pair is not formed: a sample without a finite
+    genotype --, or None where no pair of the class is formed: a refused shape, arrays beyond `budget` bytes}."""
+    out = {}
+    for ri, unit in enumerate(units):
+        if not unit["needs_kernel"] or unit["invalid"] is not None:
+            continue
+        locus = unit["locus"]
+        H, f = len(locus.haplotypes), locus.frequencies
+        for key, members in plan.compared():
+            K, F = key
+            if _identity_class_state(unit, key, len(members), budget) is not None:
+                out[(ri, key)] = None
+                continue
+            reads = np.array([len(unit["reads"][s]["counts"]) > 0 for s in members])
+            llks = np.stack([_unit_llk(unit, s, K, backend) for s in members])
+            out[(ri, key)] = identity_unit(llks, _host_log_prior(_genotype_table(H, K), H, K, F, f), error, reads)
+    return out
+
+
+def _identity_device(units, samples, ploidy_of, inbreeding_of, plan, error, budget=None):
+    """identity_host's result from the device.  Per shape group and class one likelihood pass over the class's units with reads
+    (llks64 alone, cut by the free HBM) and the evidence launch for log Z, the likelihoods kept on the device.  Then, per number of
+    haplotypes and class, as few identity launches as the budget allows (device_unit_budget over _identity_need; `budget`: bytes,
+    for the tests): all samples of the class and as many records as fit.  A launch the library refuses is run again record by
+    record; a record refused on its own is skipped for the class (None), never an invalid record.  The results are read back
+    after everything is enqueued."""
+    from math import comb
+
+    from .device import ExactIdentity, ExactModelEvidence
+
+    e = float(error)
+    out, llk, norm, pending = {}, {}, {}, []
+    dev = ev = None
+    classes = plan.compared()
+    for shape, group in _shape_groups(units, ploidy_of).items():
+        M, A, H, K = shape
+        for key, names in classes:
+            if key[0] != K:
+                continue
+            F = key[1]
+            members = [m for m in group if units[m[0]]["invalid"] is None and m[1] in names
+                       and _identity_class_state(units[m[0]], key, len(names), None) is None
+                       and len(units[m[0]]["reads"][m[1]]["counts"]) > 0]
+            todo = [members]
+            while todo:
+                part = todo.pop(0)
+                if not part:
+                    continue
+                for chunk, batch in _estimate_group_batches(units, part, shape, lambda s: 0.0, 8, prior=False):
+                    recs = sorted({ri for ri, _ in chunk})
+                    row = {ri: i for i, ri in enumerate(recs)}
+                    try:
+                        if batch is None:
+                            raise NotImplementedError
+                        llks = batch.run_llks64()
+                        if dev is None:
+                            dev, ev = ExactIdentity(), ExactModelEvidence()
+                        freqs = np.stack([units[ri]["locus"].frequencies for ri in recs])
+                        got = ev.add_group(llks, H, K, None if F is None else np.full((len(chunk), 1), F), [row[ri] for ri, _ in chunk], freqs)
+                        table = llks.view(len(chunk), -1)
+                        for i, m in enumerate(chunk):
+                            llk[m], norm[m] = table[i], got[i]
+                    except NotImplementedError:
+                        if len(chunk) > 1:
+                            todo.extend([m] for m in chunk)   # (a refused chunk again unit by unit; one refused on its own stays out)
+    by_haps = {}
+    for ri, unit in enumerate(units):
+        if unit["needs_kernel"] and unit["invalid"] is None:
+            by_haps.setdefault(len(unit["locus"].haplotypes), []).append(ri)
+    if budget is None:
+        budget = device_unit_budget(1, most=1 << 62)
+    for H, recs in by_haps.items():
+        for key, names in classes:
+            K, F = key
+            n = len(names)
+            live = []
+            for ri in recs:
+                if _identity_class_state(units[ri], key, n, budget) is not None:
+                    out[(ri, key)] = None
+                else:
+                    live.append(ri)
+            if not live:
+                continue
+            if dev is None:   # (no sample of the block has reads)
+                dev = ExactIdentity()
+            torch = dev.torch
+            G = comb(H + K - 1, K)
+            zeros = torch.zeros(G, dtype=torch.float64, device=dev.device)
+            nan = torch.full((1,), float("nan"), dtype=torch.float64, device=dev.device)
+            one = torch.zeros(1, dtype=torch.float64, device=dev.device)
+            todo = list(_blocks(live, int(budget // _identity_need(H, K, n))))
+            while todo:
+                part = todo.pop(0)
+                reads = np.array([[1 if len(units[ri]["reads"][s]["counts"]) > 0 else 0 for s in names] for ri in part], dtype=np.int32)
+                try:
+                    # (a sample with reads whose likelihood pass was refused: a NaN evidence, its pairs are not formed)
+                    stack = torch.stack([llk.get((ri, s), zeros) for ri in part for s in names]).reshape(-1)
+                    ln = torch.cat([norm[(ri, s)] if (ri, s) in norm else (nan if reads[i, k] else one)
+                                    for i, ri in enumerate(part) for k, s in enumerate(names)]).reshape(len(part), n).contiguous()
+                    freqs = np.stack([units[ri]["locus"].frequencies for ri in part])
+                    got = dev.log_bayes_factors(stack, H, K, F, np.arange(len(part)), freqs, ln, e, reads, workspace_limit=budget)
+                    pending.append((part, key, got))
+                except NotImplementedError:
+                    if len(part) > 1:
+                        todo.extend([ri] for ri in part)
+                    else:
+                        out[(part[0], key)] = None
+    for part, key, got in pending:
+        host = got.cpu().numpy()
+        for i, ri in enumerate(part):
+            out[(ri, key)] = host[i]
+    return out
+
+
+class Identity:
+    """The accumulator of `call-exact --identity`: per compared pair of samples the sum over the records of the natural log Bayes
+    factor of "the two samples carry one genotype" against "their genotypes are independent draws from the calling prior"
+    (identity_host), over the records `call-exact` sends to the kernel.  Two samples are compared where they have the same ploidy
+    and the same calling prior (the same inbreeding under --use-dirmul-prior, else the flat prior).  A (record, pair) in which a
+    sample has no finite genotype, and every pair of a record whose shape the library refuses, is left out and counted in SKIPPED:
+    skipping is per pair.  A record with a single haplotype, and a (record, pair) in which a sample has no reads, add exactly 0
+    and are counted in RECORDS.  No relatedness short of identity, no clone groups (the table lists pairs), no linkage between
+    the records.
+
+    samples: the source's; names: the samples compared, or None for all; error: the probability in [0, 1] that at a record the two
+    genotypes are independent even for one individual; min_log_bf: the rows kept are those with LOG_BF >= it (None: all);
+    frequency_source: as ModelEvidence; budget: the device bytes a launch may take (None: a share of the free memory)."""
+
+    HEADER = ("SAMPLE_1", "SAMPLE_2", "PLOIDY", "RECORDS", "SKIPPED", "LOG_BF")
+
+    def __init__(self, samples, names=None, error=0.01, min_log_bf=None, frequency_source="flat", program="mchap_amd call-exact",
+                 budget=None):
+        self.samples = list(samples)
+        self.names = None if names is None else list(names)
+        self.error = float(error)
+        if not 0.0 <= self.error <= 1.0:   # (False for NaN too)
+            raise ValueError("identity: the error lies in [0, 1]")
+        self.min_log_bf = None if min_log_bf is None else float(min_log_bf)
+        if self.min_log_bf is not None and np.isnan(self.min_log_bf):
+            raise ValueError("identity: the least LOG_BF kept is a number")
+        self.frequency_source, self.program, self.budget = frequency_source, program, budget
+        self.plan = None
+        self.sums = self.records = self.skipped = None
+        self.records_seen = 0
+
+    def resolve(self, ploidy_of, inbreeding_of):
+        """The run's IdentityPlan, formed and checked once; the pairs that are not compared are counted on stderr."""
+        import sys
+
+        plan = IdentityPlan(self.samples, self.names, ploidy_of, inbreeding_of)
+        if self.plan is None:
+            self.plan = plan
+            if plan.not_compared:
+                print("WARNING: identity: %d pairs of samples differ in ploidy or inbreeding and are not compared" % plan.not_compared,
+                      file=sys.stderr)
+            self.sums = {pair: 0.0 for pair in plan.pairs}
+            self.records = {pair: 0 for pair in plan.pairs}
+            self.skipped = {pair: 0 for pair in plan.pairs}
+        elif plan.key != self.plan.key:
+            raise ValueError("identity: the samples' ploidy or inbreeding changed between blocks")
+        return self.plan
+
+    def add_block(self, units, ploidy_of, inbreeding_of, backend=None):
+        """The records of a block (what _exact_units returned, after the frequency estimate where there is one): every (record,
+        pair) adds its term to the pair's sum, in record order, in float64 on the host.  backend: the definition on that object
+        (identity_host); None = the device."""
+        plan = self.resolve(ploidy_of, inbreeding_of)
+        self.records_seen += len(units)
+        if backend is not None:
+            got = identity_host(units, self.samples, ploidy_of, inbreeding_of, plan, self.error, backend, self.budget)
+        else:
+            got = _identity_device(units, self.samples, ploidy_of, inbreeding_of, plan, self.error, self.budget)
+        at = {key: {s: k for k, s in enumerate(members)} for key, members in plan.compared()}
+        for ri, unit in enumerate(units):
+            for pair in plan.pairs:
+                key = plan.key[pair[0]]
+                if (ri, key) in got:
+                    lbf = got[(ri, key)]
+                    term = np.nan if lbf is None else float(lbf[at[key][pair[0]], at[key][pair[1]]])
+                    if np.isnan(term):
+                        self.skipped[pair] += 1
+                        continue
+                    self.sums[pair] = self.sums[pair] + term
+                elif unit["invalid"] is not None or len(unit["locus"].haplotypes) != 1:
+                    continue   # (a record the run does not call; a single haplotype: one genotype, exactly 0)
+                self.records[pair] += 1
+        return got
+
+    def table(self):
+        """The rows, by LOG_BF descending (ties in pair order), those with LOG_BF >= min_log_bf: dicts of HEADER's names in lower
+        case."""
+        pairs = self.plan.pairs if self.plan is not None else []
+        order = sorted(range(len(pairs)), key=lambda k: -self.sums[pairs[k]])   # (stable: ties stay in pair order)
+        rows = []
+        for k in order:
+            pair = pairs[k]
+            if self.min_log_bf is not None and not self.sums[pair] >= self.min_log_bf:
+                continue
+            rows.append(dict(sample_1=pair[0], sample_2=pair[1], ploidy=self.plan.key[pair[0]][0], records=self.records[pair],
+                             skipped=self.skipped[pair], log_bf=float(self.sums[pair]) + 0.0))
+        return rows
+
+    def text(self):
+        lines = ["# %s identity; frequencies: %s; error: %g; records: %d; pairs not compared: %d"
+                 % (self.program, self.frequency_source, self.error, self.records_seen, self.plan.not_compared if self.plan is not None else 0),
+                 "\t".join(self.HEADER)]
+        for r in self.table():
+            lines.append("\t".join([r["sample_1"], r["sample_2"], "%d" % r["ploidy"], "%d" % r["records"], "%d" % r["skipped"],
+                                    "%.6f" % r["log_bf"]]))
+        return "\n".join(lines) + "\n"
+
+    def write(self, path):
+        with open(path, "w") as fh:
+            fh.write(self.text())
+
+
 def _per_sample(value, samples):
     """A scalar, or a {sample: value} mapping (the reference's per-sample ploidy / inbreeding files), as a function."""
     if isinstance(value, dict):
@@ -2432,7 +2765,7 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
                prior_frequencies_tag=None, inbreeding=None, calling=None, filter_input_haplotypes=None, read_kw=None,
                records_per_block=4096, shard=None, block_path=None, estimate_frequencies=None, estimate_tolerance=1e-6,
                estimate_path=None, model_evidence=None, snv_calls=None, allele_depths=None, cross_calls=None,
-               family_calls=None, parentage=None):
+               family_calls=None, parentage=None, identity=None):
     """`mchap call-exact` over a VCF of known haplotypes: yields one VCF record line per input record (no header).
     sample_bams: ordered mapping sample name -> BAM path (or pool -> [(sample, path)], or a ReadSource); ploidy /
     inbreeding: a value or {sample: value}.  The records are processed in blocks: the (record x sample) units of a block
@@ -2479,7 +2812,10 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
     `shard`.
 
     parentage: a Parentage over the source's samples; every block adds to it, after the frequency estimate -- so the estimated
-    prior is the one used -- (the record lines do not depend on it).  Not with `shard`: the sums of several ranks are not combined."""
+    prior is the one used -- (the record lines do not depend on it).  Not with `shard`: the sums of several ranks are not combined.
+
+    identity: an Identity over the source's samples; every block adds to it likewise, after the frequency estimate (the record
+    lines do not depend on it).  Not with `shard`."""
     from .vcfheader import report_fields
 
     if model_evidence is not None and shard is not None:
@@ -2494,9 +2830,13 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
         raise ValueError("family_calls runs as a single process: the file is not gathered from several ranks (shard)")
     if parentage is not None and shard is not None:
         raise ValueError("parentage runs as a single process: it does not combine the sums of several ranks (shard)")
+    if identity is not None and shard is not None:
+        raise ValueError("identity runs as a single process: it does not combine the sums of several ranks (shard)")
     source = _source(sample_bams, base_error_rate, use_base_phred_scores, read_kw)
     block_path = _call_block_path(block_path, source)
     samples = source.samples
+    if identity is not None and list(identity.samples) != list(samples):
+        raise ValueError("identity: its samples are not the source's")
     if parentage is not None and list(parentage.samples) != list(samples):
         raise ValueError("parentage: its samples are not the source's")
     if family_calls is not None and list(family_calls.samples) != list(samples):
@@ -2524,6 +2864,8 @@ def call_exact(vcf_path, sample_bams, ploidy=4, report=(), base_error_rate=0.002
             model_evidence.add_block(units, ploidy_of, inbreeding_of, calling)
         if parentage is not None:
             parentage.add_block(units, ploidy_of, inbreeding_of, calling)
+        if identity is not None:
+            identity.add_block(units, ploidy_of, inbreeding_of, calling)
         results = _run_exact_groups(units, ploidy_of, inbreeding_of, full, calling)
         lines = []
         for ri, unit in enumerate(units):

@@ -293,6 +293,31 @@ def parentage_log_evidence(gametes_a, gametes_b, llks, n_alleles, t_a, t_b):
     return out[0] if one else out
 
 
+def identity_log_bayes_factors(llks, log_prior=None, error=0.01):
+    """The identity evidence of every pair of samples at one record (not a reference function; the definition:
+    application.identity_unit): llks [n, G] the log likelihoods of n samples of one ploidy, log_prior [G] their normalised log
+    genotype prior (None: the flat prior), error in [0, 1].  Returns float64 [n, n], the diagonal NaN:
+        log((1 - error) sum_g post_i(g) post_j(g) / prior(g) + error)."""
+    import torch
+    from math import log
+
+    from .device import ExactIdentity, ExactModelEvidence
+
+    dev = ExactIdentity()
+    llk = np.atleast_2d(np.ascontiguousarray(llks, dtype=np.float64))
+    n, G = llk.shape
+    for_norm = for_a = llk
+    if log_prior is not None:
+        # (the given prior on top of the flat one the kernels add: its constant comes off again, half of it for the rows a)
+        lp = np.asarray(log_prior, dtype=np.float64)
+        with np.errstate(invalid="ignore"):
+            for_norm, for_a = llk + (lp + log(G)), llk + 0.5 * (lp + log(G))
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev.device)  # noqa: E731
+    # (the shape is given by the arrays alone: any (H, K) with C(H + K - 1, K) = G streams them alike -- K = 1 over G alleles)
+    norm = ExactModelEvidence(dev.device).add_group(up(for_norm).reshape(-1), G, 1, None, None, None).reshape(1, n).contiguous()
+    return dev.log_bayes_factors(up(for_a).reshape(-1), G, 1, None, None, None, norm, error).cpu().numpy()[0]
+
+
 def family_genotype_posteriors(llks_p, ploidy_p, llks_q, ploidy_q, llks_progeny, n_alleles, log_prior_p=None, log_prior_q=None,
                                gamete_error=(0, 0), frequencies=None):
     """The joint call of one nuclear family (not a reference function; the definition: application.family_unit): parents with log

@@ -20,7 +20,9 @@ depth of every allele (application.AlleleDepths), and `call-exact --cross-calls 
 again with the progeny of that cross called under their parents' cross prior (application.CrossCalls), and `call-exact --family-calls
 FILE --cross-parents P Q`, which writes it with the parents and the progeny called jointly (application.FamilyCalls), and `call-exact
 --parentage FILE --parentage-candidates A B ... [--parentage-progeny C ...] [--parentage-gamete-error E] [--parentage-top N]`, which
-writes a table that ranks every pair of candidate parents per progeny (application.Parentage).  `atomize --haplotypes FILE` is host only (mchap_amd/atomize.py)."""
+writes a table that ranks every pair of candidate parents per progeny (application.Parentage), and `call-exact --identity FILE
+[--identity-samples A B ...] [--identity-error E] [--identity-min-log-bf X]`, which writes a table that ranks the pairs of samples
+by the evidence that they are one individual (application.Identity).  `atomize --haplotypes FILE` is host only (mchap_amd/atomize.py)."""
 import argparse
 import sys
 
@@ -200,6 +202,17 @@ def build_parser(program):
                                 "not from its parent, one value in [0, 1] for every candidate (default: 0.01)")
             p.add_argument("--parentage-top", type=int, nargs=1, default=[None], metavar="N",
                            help="(not a reference flag) with --parentage: keep the first N rows of every progeny (default 0: all)")
+            p.add_argument("--identity", type=str, nargs=1, default=[None], metavar="FILE",
+                           help="(not a reference flag) write to FILE, when the run ends, a table that ranks the pairs of samples of one "
+                                "ploidy and one calling prior by the log Bayes factor of 'one genotype, read twice' against unrelated, "
+                                "summed over the records")
+            p.add_argument("--identity-samples", type=str, nargs="+", default=None, metavar="SAMPLE",
+                           help="(not a reference flag) with --identity: the samples compared, by name (default: every sample)")
+            p.add_argument("--identity-error", type=float, nargs=1, default=[None], metavar="E",
+                           help="(not a reference flag) with --identity: the probability that at a record the two genotypes are "
+                                "independent even for one individual, one value in [0, 1] (default: 0.01)")
+            p.add_argument("--identity-min-log-bf", type=float, nargs=1, default=[None], metavar="X",
+                           help="(not a reference flag) with --identity: keep the rows with LOG_BF >= X (default: all rows)")
             p.add_argument("--snv-report", type=str, nargs="+", default=None, metavar="FIELD", choices=["GP"],
                            help="(not a reference flag) with --snv-calls: GP adds the SNV genotype posteriors as a sixth FORMAT field")
     p.add_argument("--report", type=str, nargs="*", default=[],
@@ -266,7 +279,7 @@ def run(argv, out=None):
                                     read_group_field=id_field, mapping_quality=args.mapping_quality[0],
                                     skip_duplicates=args.skip_duplicates, skip_qcfail=args.skip_qcfail,
                                     skip_supplementary=args.skip_supplementary, workers=args.cores[0])
-    seed = evidence = snv_calls = allele_depths = cross_calls = family_calls = parentage = header = None
+    seed = evidence = snv_calls = allele_depths = cross_calls = family_calls = parentage = identity = header = None
     block_path = BLOCK_PATHS[args.block_path]
     if program == "assemble":
         if args.targets[0] is not None and args.region[0] is not None:
@@ -312,12 +325,14 @@ def run(argv, out=None):
             cross_calls = cross_calls_settings(args, samples, ploidy, world, header)
             family_calls = family_calls_settings(args, samples, ploidy, world, header)
             parentage = parentage_settings(args, samples, ploidy, inbreeding, tag, estimate, world)
+            identity = identity_settings(args, samples, ploidy, inbreeding, tag, estimate, world)
             records = application.call_exact(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
                                              inbreeding=inbreeding, filter_input_haplotypes=args.filter_input_haplotypes[0], shard=shard,
                                              block_path=block_path, estimate_frequencies=estimate,
                                              estimate_tolerance=1e-6 if args.estimate_tolerance[0] is None else args.estimate_tolerance[0],
                                              model_evidence=evidence, snv_calls=snv_calls, allele_depths=allele_depths,
-                                             cross_calls=cross_calls, family_calls=family_calls, parentage=parentage)
+                                             cross_calls=cross_calls, family_calls=family_calls, parentage=parentage,
+                                             identity=identity)
         else:
             seed = args.mcmc_seed[0]
             records = application.call(args.haplotypes[0], source, ploidy=ploidy, report=report, prior_frequencies_tag=tag,
@@ -358,6 +373,8 @@ def run(argv, out=None):
         family_calls.write(args.family_calls[0])
     if parentage is not None:
         parentage.write(args.parentage[0])
+    if identity is not None:
+        identity.write(args.identity[0])
     return n
 
 
@@ -372,10 +389,12 @@ CROSS_FLAGS = ("--cross-calls", "--cross-parents", "--cross-progeny", "--gamete-
 FAMILY_FLAGS = ("--family-calls",)
 # ... and the flags of the parentage table
 PARENTAGE_FLAGS = ("--parentage", "--parentage-candidates", "--parentage-progeny", "--parentage-gamete-error", "--parentage-top")
+# ... and the flags of the identity table
+IDENTITY_FLAGS = ("--identity", "--identity-samples", "--identity-error", "--identity-min-log-bf")
 
 
 def _header_argv(argv, options):
-    """The command line as the VCF header states it: without the model-evidence, SNV-file, allele-depths, cross-calls, family-calls and parentage flags and their values -- the VCF, header included,
+    """The command line as the VCF header states it: without the model-evidence, SNV-file, allele-depths, cross-calls, family-calls, parentage and identity flags and their values -- the VCF, header included,
     is byte for byte what the run writes without them.  options: the parser's option strings; a flag is resolved as argparse
     resolves it (the exact name, else the one option it is a prefix of), so an abbreviated flag is taken out too."""
     out, skipping = [], False
@@ -383,7 +402,8 @@ def _header_argv(argv, options):
         if a.startswith("--"):
             name = a.split("=", 1)[0]
             full = [name] if name in options else [o for o in options if o.startswith(name)]
-            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS + SNV_FLAGS + ALLELE_DEPTH_FLAGS + CROSS_FLAGS + FAMILY_FLAGS + PARENTAGE_FLAGS
+            skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS + SNV_FLAGS + ALLELE_DEPTH_FLAGS + CROSS_FLAGS + FAMILY_FLAGS + PARENTAGE_FLAGS + \
+                IDENTITY_FLAGS
         if not skipping:
             out.append(a)
     return out
@@ -481,6 +501,32 @@ def family_calls_settings(args, samples, ploidy, world, header_lines):
     calls = application.FamilyCalls(samples, args.cross_parents, args.cross_progeny, error, header_lines)
     calls.cross.resolve(list(samples), application._per_sample(ploidy, samples))
     return calls
+
+
+def identity_settings(args, samples, ploidy, inbreeding, tag, estimate, world):
+    """The --identity / --identity-* flags of call-exact -> an application.Identity, or None without --identity (any --identity-*
+    flag is then an error).  The pairs are checked here, before any work: the sample names, none twice, at least two, the error in
+    [0, 1]."""
+    from . import application
+
+    if args.identity[0] is None:
+        for flag, value in (("--identity-samples", args.identity_samples), ("--identity-error", args.identity_error[0]),
+                            ("--identity-min-log-bf", args.identity_min_log_bf[0])):
+            if value is not None:
+                raise ValueError("%s needs --identity" % flag)
+        return None
+    if world > 1:
+        raise ValueError("--identity runs as a single process: it does not combine the sums of several ranks (WORLD_SIZE > 1)")
+    error = 0.01 if args.identity_error[0] is None else args.identity_error[0]
+    if not 0.0 <= error <= 1.0:   # (False for NaN too)
+        raise ValueError("--identity-error: one value in [0, 1]")
+    least = args.identity_min_log_bf[0]
+    if least is not None and least != least:
+        raise ValueError("--identity-min-log-bf: a number")
+    source = "estimated" if estimate is not None else ("flat" if (tag is None or inbreeding is None) else "tag %s" % tag)
+    table = application.Identity(samples, args.identity_samples, error, least, frequency_source=source)
+    table.resolve(application._per_sample(ploidy, samples), application._per_sample(inbreeding, samples))
+    return table
 
 
 def parentage_settings(args, samples, ploidy, inbreeding, tag, estimate, world):

@@ -1097,6 +1097,79 @@ class ExactParentage:
         return out
 
 
+class ExactIdentity:
+    """Sample pairs by shared-genotype evidence for exact-caller units whose likelihoods are resident on the device
+    (mchap_exact_identity_device): per record the log Bayes factor of "one genotype read twice" against two independent draws
+    from the calling prior, for every pair of the record's samples -- one ploidy, one prior.  The definition:
+    application.identity_unit."""
+
+    def __init__(self, device=None):
+        self.torch = _torch()
+        self.device = _device(self.torch, device)
+        self.launches = 0      # calls enqueued
+
+    _tensor = ExactModelEvidence._tensor
+
+    @staticmethod
+    def workspace_bytes(n_records, n_samples, n_haps, ploidy):
+        """The bytes of workspace a call needs, or -1 for a shape the kernels refuse."""
+        return int(_lib.lib().mchap_exact_identity_workspace_bytes(int(n_records), int(n_samples), int(n_haps), int(ploidy)))
+
+    def log_bayes_factors(self, llks, n_haps, ploidy, inbreeding, rows, frequencies, log_norm, error, reads=None, workspace_limit=None, phases=3, workspace=None):
+        """The records of one shape, enqueued on torch's current stream: llks [R * n * G] a float64 tensor on the device, the n
+        samples of a record side by side; inbreeding: the one F in [0, 1) of every sample, or None for the flat prior (rows and
+        frequencies are then not used); rows [R]: each record's row of frequencies [rows, stride >= n_haps] (an array, or a
+        float64 tensor on the device); log_norm [R, n]: every sample's evidence under that prior (ExactModelEvidence.add_group, one
+        grid point), a float64 tensor on the device; error in [0, 1]; reads [R, n] of read weights, 0: no reads (None: every
+        sample has reads).  workspace_limit: the bytes the caller offers (None: what the device has free); a workspace beyond it,
+        or a shape the library refuses: NotImplementedError.  phases, workspace: for tools/identity_once.py, which times the launches
+        that form the rows a (phases = 1) and the product (phases = 2) apart over one uint8 workspace tensor of workspace_bytes.
+        Returns lbf [R, n, n] on the device, the diagonal NaN."""
+        torch, dev = self.torch, self.device
+        H, K, e = int(n_haps), int(ploidy), float(error)
+        if not 0.0 <= e <= 1.0:   # (False for NaN too)
+            raise ValueError("identity: the error lies in [0, 1]")
+        if K < 1 or K > _lib.MAX_PLOIDY_GENERAL or comb(H + K - 1, K) >= 1 << 62:
+            raise NotImplementedError("mchap_hip: ploidy %d over %d haplotypes is beyond this build's exact caller" % (K, H))
+        G = comb(H + K - 1, K)
+        assert log_norm.dtype == torch.float64 and log_norm.is_contiguous() and log_norm.dim() == 2
+        R, n = int(log_norm.shape[0]), int(log_norm.shape[1])
+        assert llks.dtype == torch.float64 and llks.is_contiguous() and llks.numel() == R * n * G
+        d_fr, stride, F = None, 0, None
+        if inbreeding is not None:
+            F = C.c_double(float(inbreeding))
+            if not 0.0 <= F.value < 1.0:
+                raise ValueError("identity: F must lie in [0, 1)")
+            table = self._tensor(frequencies, torch.float64, np.float64)
+            at = np.asarray(rows, dtype=np.int64)
+            assert table.dim() == 2 and int(table.shape[1]) >= H and at.shape == (R,)
+            assert R == 0 or (int(at.min()) >= 0 and int(at.max()) < int(table.shape[0]))
+            d_fr = table[torch.from_numpy(at).to(dev)].contiguous()
+            stride = int(d_fr.shape[1])
+        d_reads = None
+        if reads is not None:
+            w = np.ascontiguousarray(np.asarray(reads) != 0, dtype=np.int32)
+            assert w.shape == (R, n)
+            d_reads = torch.from_numpy(w).to(dev)
+        out = torch.empty((R, n, n), dtype=torch.float64, device=dev)
+        if R == 0 or n == 0:
+            return out
+        wsb = self.workspace_bytes(R, n, H, K)
+        limit = workspace_limit
+        if limit is None:
+            limit, _ = torch.cuda.mem_get_info()
+        if wsb < 0 or wsb > limit:
+            raise NotImplementedError("mchap_hip: identity of %d records x %d samples of ploidy %d over %d haplotypes: the shape is "
+                                      "refused, or its workspace does not fit the device" % (R, n, K, H))
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev) if workspace is None else workspace
+        assert ws.numel() >= wsb
+        _lib.check(_lib.lib().mchap_exact_identity_device(
+            R, n, _ptr(llks), H, K, None if F is None else C.addressof(F), _ptr(d_fr), stride, _ptr(log_norm), C.c_double(e),
+            _ptr(d_reads), _ptr(out), int(phases), _ptr(ws), C.c_int64(wsb), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        self.launches += 1
+        return out
+
+
 class ExactFamily:
     """The parents and the progeny of one cross called jointly for exact-caller units whose likelihoods are resident on the device
     (mchap_exact_family_device): per record the exact joint posterior of the two parents and all progeny, its marginals and every
