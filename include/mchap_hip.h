@@ -573,6 +573,41 @@ int mchap_exact_identity_device(int n_records, int n_samples, const double *llks
                                 const double *frequencies, int stride, const double *log_norm, double error, const int32_t *reads,
                                 double *lbf, int phases, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Selfed parents per progeny (call-exact --parentage-selfings).  mchap_exact_selfing_prior_device: the inputs of
+ * mchap_exact_gametes_device -- n_units candidate units of one shape (n_haps, even ploidy K, t = K / 2), llks64 [n_units][G],
+ * inbreeding [n_units] or NULL for the flat prior, unit_row and frequencies [rows][stride], gamete_error [n_units] in [0, 1] --; out
+ * log_self [n_units][G], self_prior [n_units][G] (or NULL) and log_norm [n_units] (or NULL): the genotype prior of a progeny of
+ * ploidy K whose two gametes are two meioses of ONE genotype drawn from the unit's posterior p,
+ *   S[gc] = sum_g p[g] sum_{a in gc, |a| = t} gamma(a | g) gamma(gc - a | g),  gamma(a | g) = (1 - e) hyp(a | g) + e Mult(a; t, f),
+ * its logarithm (exactly -inf where every product is 0) and the unit's normaliser.  It is formed as
+ *   ((1 - e)(1 - e)) (D[gc] / C(K, t)^2) + (e (1 - e)) E[gc] + (e e) Mult(gc; K, f)
+ * with D the pairs (a, gc - a) summed over the genotypes that hold both, in VCF order of a and of the complement of their union, and E
+ * the two mixed products of the error-free gamete table with Mult(.; t, f) -- never as the gamete table's product with itself plus a
+ * correction.  One lane owns each cell and every sum has a fixed order: equal inputs give equal bits whatever the unit's place in
+ * the batch.  A unit without a finite genotype has NaN throughout (log_norm as the gamete entry leaves it).  `workspace`:
+ * mchap_exact_selfing_prior_workspace_bytes (the posteriors, the error-free gamete tables, the gamete entry's own); -1, with the call
+ * itself MCHAP_ERR_LIMIT, for a ploidy beyond MCHAP_MAX_PLOIDY_DENOVO, 2^62 genotypes or more, or tables beyond 64 KB of LDS
+ * (n_haps x ploidy above about 8000).
+ *
+ * mchap_exact_selfing_evidence_device: n_records records of one shape, n_candidates rows self_prior [n_records][n_candidates][G] (S, not
+ * its logarithm), n_progeny progeny of ploidy K with llks_c [n_records][n_progeny][G]:
+ *   log_z[r][c][i] = m_c + log sum_gc S[r][i][gc] exp(llks_c[r][c][gc] - m_c),  m_c = max llks_c[r][c]
+ * each exp formed once per (progeny, genotype) for every candidate; per tile of 4096 genotypes a lane adds its 16 terms in order,
+ * then the wavefront's butterfly, the four wavefronts in order, and the tiles in tile order.  progeny_reads [n_records][n_progeny]
+ * (or NULL): 0 = no reads, the likelihoods are not read and the entries are exactly 0.  A NaN row of self_prior gives NaN in its
+ * column alone; a NaN likelihood, or none that is finite, NaN throughout the progeny; a sum of 0 exactly -inf.  `workspace`:
+ * mchap_exact_selfing_evidence_workspace_bytes, -1 (the call: MCHAP_ERR_LIMIT) for a refused shape; a workspace smaller than asked is
+ * MCHAP_ERR_LIMIT.  Both enqueue on `stream`, no synchronisation, and allocate nothing. */
+int64_t mchap_exact_selfing_prior_workspace_bytes(int n_units, int n_haps, int ploidy);
+int mchap_exact_selfing_prior_device(int n_units, const double *llks64, int n_haps, int ploidy, const double *inbreeding,
+                                     const int32_t *unit_row, const double *frequencies, int stride, const double *gamete_error,
+                                     double *log_self, double *self_prior, double *log_norm, void *workspace,
+                                     int64_t workspace_bytes, void *stream);
+int64_t mchap_exact_selfing_evidence_workspace_bytes(int n_records, int n_progeny, int n_candidates, int n_haps, int ploidy);
+int mchap_exact_selfing_evidence_device(int n_records, int n_progeny, int n_candidates, const double *self_prior, const double *llks_c,
+                                        const int32_t *progeny_reads, int n_haps, int ploidy, double *log_z, void *workspace,
+                                        int64_t workspace_bytes, void *stream);
+
 /* Summaries of given posterior arrays [U][G] (calling.exact.posterior_allele_frequencies 332-369, the sum of
  * alternate_dosage_posteriors 372-407 for the array's mode): device pointers, any output may be NULL. */
 int mchap_exact_posterior_summaries_batch_device(int n_units, const double *posteriors, int64_t n_genotypes, int ploidy,

@@ -226,6 +226,12 @@ def lib():
         L.mchap_exact_identity_workspace_bytes.restype = C.c_int64
         L.mchap_exact_identity_device.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                   C.c_double] + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        L.mchap_exact_selfing_prior_workspace_bytes.restype = C.c_int64
+        L.mchap_exact_selfing_prior_device.argtypes = [C.c_int, C.c_void_p] + [C.c_int] * 2 + [C.c_void_p] * 3 + [C.c_int] + \
+            [C.c_void_p] * 5 + [C.c_int64, C.c_void_p]
+        L.mchap_exact_selfing_evidence_workspace_bytes.restype = C.c_int64
+        L.mchap_exact_selfing_evidence_device.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p] * 2 + \
+            [C.c_int64, C.c_void_p]
         L.mchap_call_mcmc_workspace_bytes.restype = C.c_int64
         L.mchap_call_mcmc_workspace_bytes_for.restype = C.c_int64
         L.mchap_timer_ms.restype = C.c_double
@@ -334,6 +340,10 @@ EXPORTS = [
     "mchap_exact_parentage_population_device",
     "mchap_exact_identity_workspace_bytes",
     "mchap_exact_identity_device",
+    "mchap_exact_selfing_prior_workspace_bytes",
+    "mchap_exact_selfing_prior_device",
+    "mchap_exact_selfing_evidence_workspace_bytes",
+    "mchap_exact_selfing_evidence_device",
     "mchap_exact_posterior_summaries_batch_device",
     "mchap_exact_posterior_summaries",
     "mchap_call_mcmc_workspace_bytes",

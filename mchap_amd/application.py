@@ -1303,6 +1303,123 @@ def cross_prior_unit(llk_p, K_p, F_p, llk_q, K_q, F_q, H, f, gamete_error=(0.01,
     return out
 
 
+def _dosage_ranks(d):
+    """int64 [N]: the VCF index of the multisets with dosages d [N, H] (every row of one size)."""
+    d = np.asarray(d, dtype=np.int64)
+    k = int(d[0].sum()) if len(d) else 0
+    if k == 0:
+        return np.zeros(len(d), dtype=np.int64)
+    g = np.repeat(np.tile(np.arange(d.shape[1]), len(d)), d.reshape(-1)).reshape(len(d), k)   # (ascending within a row)
+    return _multiset_ranks(g)
+
+
+def selfing_prior(p, K, H, f, error):
+    """float64 [G]: the genotype prior of a progeny of ploidy K whose two gametes are two meioses of ONE genotype of even ploidy K
+    drawn from the posterior p [G] (VCF order), t = K / 2, frequencies f [H], gamete error e,
+        S[gc] = sum_g p[g] sum_{a in gc, |a| = t} gamma(a | g) gamma(gc - a | g),   gamma(a | g) = (1 - e) hyp(a | g) + e Mult(a; t, f)
+    (reference mchap/pedigree/prior.py trio_log_pmf with one genotype as both parents and lambda = 0), in the kernel's expanded form
+    and order (exact_selfing_prior_kernel):
+        J[a][b] = sum_r p[(a u b) + r] prod_h C(c_h, a_h) C(c_h, b_h)     over the complements r of the multiset union a u b, in VCF
+                                                                         order of r (one term after the other); p <= 0 or NaN: 0
+        D[gc]   = sum_a w J[a][gc - a],  E[gc] = sum_a w (gam[a] m[gc - a] + m[a] gam[gc - a])
+                                                                         over the sub-multisets a of gc with rank a <= rank (gc - a),
+                                                                         in VCF order of a; w = 2 off the diagonal, else 1
+        S[gc]   = ((1 - e)(1 - e)) (D[gc] / C(K, t)^2) + (e (1 - e)) E[gc] + (e e) Mult(gc; K, f)
+    with gam the error-free gamete table (gamete_table at error 0) and m = Mult(.; t, f) (population_gametes).  The two gametes are
+    dependent given the reads: unless p is one-hot this is NOT the cross prior of the gamete table with itself.  Exactly 0 where
+    every product is 0 (e = 0, or a zero frequency); NaN throughout for a posterior with a NaN."""
+    from math import comb
+
+    if K < 2 or K % 2:
+        raise ValueError("a parent of ploidy %d: the gametes of an even ploidy alone are formed" % K)
+    t, e = K // 2, float(error)
+    p = np.asarray(p, dtype=np.float64)
+    f = np.asarray(f, dtype=np.float64)
+    G = comb(H + K - 1, K)
+    assert p.shape == (G,)
+    if np.any(np.isnan(p)):
+        return np.full(G, np.nan)
+    a = _genotype_table(H, t)
+    da = _dosages(a, H)
+    gam, m = gamete_table(p, H, K, f, 0.0), population_gametes(H, t, f)
+    ia, ib = np.triu_indices(len(a))          # (row-major: for one gc its pairs come in VCF order of a)
+    xa, xb = da[ia], da[ib]
+    union = np.maximum(xa, xb)
+    size = union.sum(axis=1)
+    binom = np.array([[comb(n, k) for k in range(K + 1)] for n in range(K + 1)], dtype=np.int64)
+    pp = np.where(p > 0.0, p, 0.0)
+    J = np.zeros(len(ia))
+    for u in range(t, K + 1):
+        sel = np.nonzero(size == u)[0]
+        if not len(sel):
+            continue
+        dr = _dosages(_genotype_table(H, K - u), H) if K > u else np.zeros((1, H), dtype=np.int64)
+        for c in range(len(dr)):
+            d = union[sel] + dr[c][None, :]
+            w = np.prod(binom[d, xa[sel]] * binom[d, xb[sel]], axis=1)
+            J[sel] = J[sel] + pp[_dosage_ranks(d)] * w
+    wt = np.where(ia == ib, 1.0, 2.0)
+    tD = wt * J
+    tE = wt * (gam[ia] * m[ib] + m[ia] * gam[ib])
+    gc = _dosage_ranks(xa + xb)
+    D, E = np.zeros(G), np.zeros(G)
+    lo = np.searchsorted(ia, np.arange(len(a) + 1))
+    for i in range(len(a)):                   # (for one a the genotypes a + b are distinct: every cell takes its terms in the order of a)
+        s = slice(lo[i], lo[i + 1])
+        D[gc[s]] += tD[s]
+        E[gc[s]] += tE[s]
+    pairs = float(comb(K, t))
+    return ((1.0 - e) * (1.0 - e)) * (D / (pairs * pairs)) + (e * (1.0 - e)) * E + (e * e) * population_gametes(H, K, f)
+
+
+def selfing_evidence(S, llk_c):
+    """float64 [n]: log sum_gc S[i][gc] exp(llk_c[gc]) for the rows S [n, G] (selfing_prior) and a progeny's log likelihoods llk_c [G],
+    as m + log sum_gc S[i][gc] exp(llk_c[gc] - m), m = max llk_c, in the kernel's order (selfing_evidence_kernel): per tile of 4096
+    genotypes 256 strided partial sums (gc = l, l + 256, ... one term after the other), the butterfly over each 64 of them (32, 16,
+    8, 4, 2, 1), the four results in order; then the tiles in order.  llk_c None: a progeny without reads, exactly 0.  A NaN row
+    gives NaN in its entry alone; a NaN likelihood, or none that is finite, NaN throughout; a sum of 0 exactly -inf."""
+    S = np.atleast_2d(np.asarray(S, dtype=np.float64))
+    if llk_c is None:
+        return np.zeros(len(S))
+    llk = np.asarray(llk_c, dtype=np.float64)
+    G = len(llk)
+    assert S.shape[1] == G
+    lanes, wave, tile = 256, 64, 4096
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        m = float("nan") if np.any(np.isnan(llk)) else float(np.max(llk))
+        T = np.exp(llk - m)
+        total = np.zeros(len(S))
+        lane = np.arange(wave)
+        for t0 in range(0, G, tile):
+            part = np.zeros((lanes, len(S)))
+            for lo in range(t0, min(t0 + tile, G), lanes):
+                n = min(lanes, G - lo)
+                part[:n] = part[:n] + S.T[lo:lo + n] * T[lo:lo + n, None]
+            v = part.reshape(lanes // wave, wave, len(S))
+            for o in (32, 16, 8, 4, 2, 1):
+                v = v + v[:, lane ^ o]
+            z = v[0, 0]
+            for w in range(1, lanes // wave):
+                z = z + v[w, 0]
+            total = total + z
+        return m + np.log(total)
+
+
+def selfing_prior_unit(llk, K, F, H, f, gamete_error=0.01, llk_c=None):
+    """The definition for one selfed parent, in float64, beside cross_prior_unit: the parent's posterior under its calling prior (F
+    None: the flat genotype prior; f [H] the record's calling frequencies, None: flat), the selfing prior of its progeny
+    (selfing_prior) and -- with the progeny's likelihoods llk_c [G] -- the evidence under it (selfing_evidence).  Returns a dict: p,
+    log_norm, S, log_s, and with llk_c also log_z.  A parent without a finite genotype gives NaN throughout."""
+    fr = np.full(H, 1.0 / H) if f is None else np.asarray(f, dtype=np.float64)
+    p, norm = _unit_posterior(llk, H, K, F, fr)
+    S = selfing_prior(p, K, H, fr, gamete_error)
+    with np.errstate(divide="ignore"):
+        out = dict(p=p, log_norm=norm, S=S, log_s=np.log(S))
+    if llk_c is not None:
+        out["log_z"] = float(selfing_evidence(S, llk_c)[0])
+    return out
+
+
 class Cross:
     """One cross of a run: the two parents, the progeny (None: every other sample of ploidy t_P + t_Q) and the gamete errors
     (one value, or one per parent).  resolve() checks it against the samples' ploidies."""
@@ -1913,6 +2030,7 @@ class FamilyCalls:
 PARENTAGE_TMAX = 7          # the largest gamete size the parentage kernel takes (exact_parentage_kernel.hpp)
 PARENTAGE_LDS = 160 * 1024  # ... and the LDS its rank table shares with PARENTAGE_STAGE bytes of staged rows
 PARENTAGE_STAGE = 16 * 256 * 8
+SELFING_LDS = 64 * 1024     # the LDS the selfing kernels' tables may take (exact_selfing_api.hip LDS_MOST)
 UNKNOWN_PARENT = "."
 
 
@@ -1973,9 +2091,11 @@ class ParentagePlan:
     hypothesis order -- every pair (i, j), i < j in candidate order, with t_i + t_j = K_c, then every (i, '.') with 1 <= K_c - t_i,
     the other gamete the population's, then ('.', '.') --, a pair that holds c itself left out.  launches[K_c]: the (t_a, t_b),
     t_a <= t_b, the rows of a progeny of ploidy K_c need; where(c, row) = ((t_a, t_b), i, j): the entry of that launch's
-    [n_a + 1, n_b + 1] matrix -- the candidates of a gamete size in candidate order, the population's row last."""
+    [n_a + 1, n_b + 1] matrix -- the candidates of a gamete size in candidate order, the population's row last.  selfings: a
+    progeny of ploidy K_c gains a row (i, i) for every candidate i != c with 2 t_i = K_c, after the pairs and before the (i, '.');
+    selfed[K_c]: those candidates, in candidate order -- the rows of the selfing launch of that ploidy (no parentage launch)."""
 
-    def __init__(self, samples, candidates, progeny, ploidy_of):
+    def __init__(self, samples, candidates, progeny, ploidy_of, selfings=False):
         samples, candidates = list(samples), list(candidates)
         progeny = [s for s in samples if s not in candidates] if progeny is None else list(progeny)
         if not candidates:
@@ -1996,15 +2116,20 @@ class ParentagePlan:
         self.by_size = {}
         for s in candidates:
             self.by_size.setdefault(self.size[s], []).append(s)
-        self.hypotheses, self.launches = {}, {}
+        self.selfings = bool(selfings)
+        self.hypotheses, self.launches, self.selfed = {}, {}, {}
         for c in self.progeny:
             Kc = self.ploidy[c]
-            rows = [(p, q) for i, p in enumerate(candidates) for q in candidates[i + 1:]
-                    if c not in (p, q) and self.size[p] + self.size[q] == Kc]
-            rows += [(p, UNKNOWN_PARENT) for p in candidates if p != c and Kc - self.size[p] >= 1]
-            self.hypotheses[c] = rows + [(UNKNOWN_PARENT, UNKNOWN_PARENT)]
+            pairs = [(p, q) for i, p in enumerate(candidates) for q in candidates[i + 1:]
+                     if c not in (p, q) and self.size[p] + self.size[q] == Kc]
+            selfs = [(p, p) for p in candidates if p != c and 2 * self.size[p] == Kc] if self.selfings else []
+            singles = [(p, UNKNOWN_PARENT) for p in candidates if p != c and Kc - self.size[p] >= 1]
+            self.hypotheses[c] = pairs + selfs + singles + [(UNKNOWN_PARENT, UNKNOWN_PARENT)]
+            if selfs:
+                both = set(self.selfed.get(Kc, ())) | {p for p, _ in selfs}
+                self.selfed[Kc] = [p for p in candidates if p in both]
             need = self.launches.setdefault(Kc, [])
-            for row in rows:
+            for row in pairs + singles:
                 shape = self.where(c, row)[0]
                 if shape not in need:
                     need.append(shape)
@@ -2025,6 +2150,10 @@ class ParentagePlan:
         """The candidates in the rows of progeny c."""
         return [s for s in self.candidates if any(s in row for row in self.hypotheses[c])]
 
+    def selfs(self, c):
+        """The selfed candidates in the rows of progeny c, in row order."""
+        return [p for p, q in self.hypotheses[c] if p == q and p != UNKNOWN_PARENT]
+
 
 def _parentage_need(H, shape, n_b):
     """Device bytes of one (record, progeny) of a parentage launch: the sums over b of every (column, gamete a), its likelihoods
@@ -2035,6 +2164,28 @@ def _parentage_need(H, shape, n_b):
     return (n_b * comb(H + ta - 1, ta) + comb(H + ta + tb - 1, ta + tb)) * 8 + 4096
 
 
+def _selfing_shape_ok(H, K):
+    """Whether the selfing launches take a candidate of ploidy K over H haplotypes (mchap_exact_selfing_prior_workspace_bytes >= 0):
+    the rank table, and the prior tables of the gamete kernel, within 64 KB of LDS."""
+    from math import comb
+
+    from ._lib import MAX_PLOIDY_GENERAL
+
+    tail = (17 * 17 + 1) // 2
+    return (2 <= K <= MAX_PLOIDY_GENERAL and K % 2 == 0 and comb(H + K - 1, K) < 1 << 62
+            and max(H * K + 2 * (K + 1) + H, H * (K + 1) + (K + 1) + H + 1) + tail <= SELFING_LDS // 8)
+
+
+def _selfing_need(H, K, n):
+    """Device bytes of the selfing launches: (one candidate unit of the prior launch -- its posterior, S, log S, the gamete table and
+    the evidence pass' partials --, one (record, progeny) of the evidence launch -- its likelihoods, a row of results and the tiles'
+    sums of every candidate)."""
+    from math import comb
+
+    G = comb(H + K - 1, K)
+    return (3 * G + comb(H + K // 2 - 1, K // 2)) * 8 + 8192, (G + n * (1 + (G + 4095) // 4096)) * 8 + 4096
+
+
 def _parentage_progeny_state(unit, plan, c, missing, budget):
     """None where the rows of progeny c can be formed at this record, else why not: a refused shape, a candidate of its rows
     without gametes (`missing`: those candidates), a launch beyond the budget."""
@@ -2042,31 +2193,40 @@ def _parentage_progeny_state(unit, plan, c, missing, budget):
     Kc = plan.ploidy[c]
     if not _cross_evaluable(unit, Kc) or not all(_parentage_shape_ok(H, *shape) for shape in plan.launches[Kc]):
         return "shape"
+    if plan.selfs(c) and not _selfing_shape_ok(H, Kc):
+        return "shape"
     if any(s in missing for s in plan.used(c)):
         return "candidate"
     if budget is not None and any(_parentage_need(H, shape, len(plan.by_size.get(shape[1], ())) + 1) > budget for shape in plan.launches[Kc]):
         return "budget"
+    if budget is not None and plan.selfs(c) and max(_selfing_need(H, Kc, len(plan.selfed[Kc]))) > budget:
+        return "budget"
     return None
 
 
-def parentage_host(units, samples, ploidy_of, inbreeding_of, plan, gamete_error, backend, budget=None):
+def parentage_host(units, samples, ploidy_of, inbreeding_of, plan, gamete_error, backend, budget=None, selfings=False):
     """The definition of the parentage evidence over a block, in float64 on `backend` (an object with the reference's
     genotype_likelihoods; the oracle in the CPU tests).  For every record that needs the kernel and every progeny c of `plan`
     (ParentagePlan), per row (P, Q) of plan.hypotheses[c]
         lbf = log sum_{a, b} gam'_P[a] gam'_Q[b] exp(llk_c[rank(a + b)]) - log Z_pop,c                       (parentage_unit)
     with gam' the candidate's gamete table under its calling prior at `gamete_error` (gamete_table), the population's for '.'
     (population_gametes), and Z_pop,c the progeny's evidence under its own calling prior; ('.', '.') is exactly 0, and so is every
-    row of a progeny without reads.  Returns {(record index, progeny): float64 [rows] -- or None where the rows are not formed: a
+    row of a progeny without reads.  A selfing row (P, P) -- a plan with selfings; `selfings` must say the same -- is
+        lbf = log sum_gc S_P[gc] exp(llk_c[gc]) - log Z_pop,c                                                  (selfing_evidence)
+    with S_P the selfing prior of the candidate's posterior (selfing_prior): two meioses of ONE genotype.  Returns {(record index, progeny): float64 [rows] -- or None where the rows are not formed: a
     candidate of the progeny's rows or the progeny itself without a finite genotype, a refused shape, a launch beyond `budget`
     bytes}: the (record, progeny) is then left out of every row."""
     e = float(gamete_error)
+    if bool(selfings) != plan.selfings:
+        raise ValueError("parentage: the plan was formed %s selfings" % ("with" if plan.selfings else "without"))
+    selfed = {s for names in plan.selfed.values() for s in names}
     out = {}
     for ri, unit in enumerate(units):
         if not unit["needs_kernel"] or unit["invalid"] is not None:
             continue
         locus = unit["locus"]
         H, f = len(locus.haplotypes), locus.frequencies
-        gam, missing = {}, set()
+        gam, missing, self_prior = {}, set(), {}
         for s in plan.candidates:
             K = plan.ploidy[s]
             if not _cross_evaluable(unit, K):
@@ -2077,6 +2237,8 @@ def parentage_host(units, samples, ploidy_of, inbreeding_of, plan, gamete_error,
                 missing.add(s)
             else:
                 gam[s] = gamete_table(p, H, K, f, e)
+                if s in selfed and _selfing_shape_ok(H, K):
+                    self_prior[s] = selfing_prior(p, K, H, f, e)
         tables = {}
         for c in plan.progeny:
             rows = plan.hypotheses[c]
@@ -2097,15 +2259,51 @@ def parentage_host(units, samples, ploidy_of, inbreeding_of, plan, gamete_error,
                     pop = population_gametes(H, t, f)
                     tables[t] = np.stack([gam.get(s, np.full(len(pop), np.nan)) for s in plan.by_size.get(t, ())] + [pop])
             z = {shape: parentage_unit(tables[shape[0]], tables[shape[1]], llk_c, H, *shape) for shape in plan.launches[Kc]}
+            selfs = plan.selfs(c)
+            zs = selfing_evidence(np.stack([self_prior[s] for s in selfs]), llk_c) if selfs else None
             lbf = np.zeros(len(rows))
             for k, row in enumerate(rows[:-1]):
+                if row[0] == row[1]:
+                    lbf[k] = zs[selfs.index(row[0])] - norm
+                    continue
                 shape, i, j = plan.where(c, row)
                 lbf[k] = z[shape][i, j] - norm
             out[(ri, c)] = lbf
     return out
 
 
-def _parentage_device(units, samples, ploidy_of, inbreeding_of, plan, gamete_error, budget=None):
+def _parentage_in_parts(key, need, live, progeny, budget, state, llk, zeros, pending, launch):
+    """One kind of launch (`key`: a pair of gamete sizes, or "selfing") over the records `live` of one number of haplotypes and the
+    `progeny` of one ploidy: launch(positions in `live`, the stacked likelihoods, flags [records, progeny]) takes all progeny and
+    as many records as `budget` bytes allow at `need` bytes a (record, progeny); a refused launch is run again record by record,
+    then progeny by progeny, and what is refused on its own is marked in `state`.  The results go to `pending` as (records,
+    progeny, key, tensor).  llk: {(record, progeny): its likelihoods on the device}; zeros: the row that stands for one without."""
+    import torch
+
+    per_launch = int(budget // max(need * len(progeny), 1))
+    if per_launch >= 1:
+        todo = [(part, progeny) for part in _blocks(list(range(len(live))), per_launch)]
+    else:
+        todo = [([i], part) for i in range(len(live)) for part in _blocks(progeny, max(1, int(budget // need)))]
+    while todo:
+        part, prog = todo.pop(0)
+        on = [[1 if state[(live[i], c)] is None and (live[i], c) in llk else 0 for c in prog] for i in part]
+        if not any(any(r) for r in on):
+            continue
+        try:
+            stack = torch.stack([llk.get((live[i], c), zeros) for i in part for c in prog]).reshape(-1)
+            got = launch(part, stack, np.array(on, dtype=np.int32).reshape(len(part), len(prog)))
+            pending.append(([live[i] for i in part], prog, key, got))
+        except NotImplementedError:
+            if len(part) > 1:
+                todo.extend(([i], prog) for i in part)
+            elif len(prog) > 1:
+                todo.extend((part, [c]) for c in prog)
+            else:
+                state[(live[part[0]], prog[0])] = "refused"
+
+
+def _parentage_device(units, samples, ploidy_of, inbreeding_of, plan, gamete_error, budget=None, selfings=False):
     """parentage_host's result from the device.  Per shape group one likelihood pass (llks64 alone, cut by the free HBM): the
     candidates' units go through the gamete launch (device.ExactParentage.gametes), the progeny's through the evidence launch for
     Z_pop,c, their likelihoods kept on the device.  Then, per number of haplotypes, per progeny ploidy and per pair of gamete
@@ -2113,12 +2311,16 @@ def _parentage_device(units, samples, ploidy_of, inbreeding_of, plan, gamete_err
     budget allows (device_unit_budget over _parentage_need; `budget`: bytes, for the tests): all progeny of the ploidy and as many
     records as fit.  A launch the library refuses is run again in smaller parts, first record by record, then progeny by progeny;
     what is refused on its own is skipped (None), never an invalid record.  The results are read back after everything is
-    enqueued."""
-    from .device import ExactModelEvidence, ExactParentage
+    enqueued.  With selfings the candidates of a selfing row go through the selfing-prior launch too (device.ExactSelfing), from
+    the likelihood pass already made for their gamete launch; then one selfing-evidence launch per progeny ploidy over all its
+    selfed candidates, cut and run again in parts as the parentage launch is."""
+    from .device import ExactModelEvidence, ExactParentage, ExactSelfing
 
     e = float(gamete_error)
-    out, llk, norm, gam, pending, flags = {}, {}, {}, {}, [], []
-    dev = ev = torch_isnan = None
+    if bool(selfings) != plan.selfings:
+        raise ValueError("parentage: the plan was formed %s selfings" % ("with" if plan.selfings else "without"))
+    out, llk, norm, gam, pending, flags, self_prior = {}, {}, {}, {}, [], [], {}
+    dev = ev = sdev = torch_isnan = None
     for shape, group in _shape_groups(units, ploidy_of).items():
         M, A, H, K = shape
         for role in ("candidate", "progeny"):
@@ -2148,6 +2350,25 @@ def _parentage_device(units, samples, ploidy_of, inbreeding_of, plan, gamete_err
                                 for i, key in enumerate(chunk):
                                     gam[key] = got[i]
                                 flags.append((chunk, torch_isnan(got[:, 0])))
+                                # the selfed candidates of the chunk: their selfing priors from the same likelihoods
+                                idx = [i for i, (_, s) in enumerate(chunk) if s in plan.selfed.get(K, ()) and _selfing_shape_ok(H, K)]
+                                fit = len(idx) if budget is None else max(1, int(budget // _selfing_need(H, K, 1)[0]))
+                                todo_self = list(_blocks(idx, max(fit, 1)))
+                                while todo_self:
+                                    idx = todo_self.pop(0)
+                                    if not idx:
+                                        continue
+                                    if sdev is None:
+                                        sdev = ExactSelfing()
+                                    try:
+                                        sub = llks if len(idx) == len(chunk) else llks.view(len(chunk), -1)[idx].contiguous().reshape(-1)
+                                        got_s = sdev.selfing_prior(sub, H, K, None if flat else [inbreeding_of(chunk[i][1]) for i in idx],
+                                                                   [rows[i] for i in idx], freqs, e, workspace_limit=budget)[1]
+                                        for k, i in enumerate(idx):
+                                            self_prior[chunk[i]] = got_s[k]
+                                    except NotImplementedError:
+                                        if len(idx) > 1:
+                                            todo_self.extend([i] for i in idx)   # (one refused on its own stays out)
                             else:
                                 grid = None if flat else np.array([[inbreeding_of(s)] for _, s in chunk], dtype=np.float64)
                                 got = ev.add_group(llks, H, K, grid, rows, freqs)
@@ -2175,6 +2396,8 @@ def _parentage_device(units, samples, ploidy_of, inbreeding_of, plan, gamete_err
                     reads = len(units[ri]["reads"][c]["counts"]) > 0
                     if why is None and reads and (ri, c) not in llk:
                         why = "likelihoods"
+                    if why is None and any((ri, s) not in self_prior for s in plan.selfs(c)):
+                        why = "selfing"
                     state[(ri, c)] = why
                     if why is None and reads and ri not in live:
                         live.append(ri)
@@ -2192,29 +2415,16 @@ def _parentage_device(units, samples, ploidy_of, inbreeding_of, plan, gamete_err
             zeros = torch.zeros(dev.cross._shape(H, Kc), dtype=torch.float64, device=dev.device)
             for shape in shapes:
                 ta, tb = shape
-                need = _parentage_need(H, shape, int(tables[tb].shape[1]))
-                per_launch = int(budget // max(need * len(progeny), 1))
-                if per_launch >= 1:
-                    todo = [(part, progeny) for part in _blocks(list(range(len(live))), per_launch)]
-                else:
-                    todo = [([i], part) for i in range(len(live)) for part in _blocks(progeny, max(1, int(budget // need)))]
-                while todo:
-                    part, prog = todo.pop(0)
-                    on = [[1 if state[(live[i], c)] is None and (live[i], c) in llk else 0 for c in prog] for i in part]
-                    if not any(any(r) for r in on):
-                        continue
-                    try:
-                        stack = torch.stack([llk.get((live[i], c), zeros) for i in part for c in prog]).reshape(-1)
-                        got = dev.log_evidence(tables[ta][part].contiguous(), tables[tb][part].contiguous(), stack, H, ta, tb,
-                                               np.array(on, dtype=np.int32).reshape(len(part), len(prog)), workspace_limit=budget)
-                        pending.append(([live[i] for i in part], prog, shape, got))
-                    except NotImplementedError:
-                        if len(part) > 1:
-                            todo.extend(([i], prog) for i in part)
-                        elif len(prog) > 1:
-                            todo.extend((part, [c]) for c in prog)
-                        else:
-                            state[(live[part[0]], prog[0])] = "refused"
+                _parentage_in_parts(shape, _parentage_need(H, shape, int(tables[tb].shape[1])), live, progeny, budget, state, llk, zeros, pending,
+                                    lambda part, stack, on, ta=ta, tb=tb: dev.log_evidence(
+                                        tables[ta][part].contiguous(), tables[tb][part].contiguous(), stack, H, ta, tb, on, workspace_limit=budget))
+            cands = plan.selfed.get(Kc, [])
+            selfed_progeny = [c for c in progeny if plan.selfs(c)]
+            if cands and selfed_progeny:
+                nan = torch.full((int(zeros.numel()),), float("nan"), dtype=torch.float64, device=dev.device)
+                priors = torch.stack([torch.stack([self_prior.get((ri, s), nan) for s in cands]) for ri in live])
+                _parentage_in_parts("selfing", _selfing_need(H, Kc, len(cands))[1], live, selfed_progeny, budget, state, llk, zeros, pending,
+                                    lambda part, stack, on: sdev.log_evidence(priors[part].contiguous(), stack, H, Kc, on, workspace_limit=budget))
     # a candidate without a finite genotype: a NaN row of its table
     bad = {}
     for chunk, isnan in flags:
@@ -2246,11 +2456,15 @@ def _parentage_device(units, samples, ploidy_of, inbreeding_of, plan, gamete_err
             if id(t) not in host_norm:
                 host_norm[id(t)] = (t, t.cpu().numpy())
             ln = float(host_norm[id(t)][1][at, 0])
-            if not np.isfinite(ln) or any((ri, c, shape) not in z for shape in plan.launches[plan.ploidy[c]]):
+            selfs = plan.selfs(c)
+            if not np.isfinite(ln) or any((ri, c, shape) not in z for shape in plan.launches[plan.ploidy[c]] + (["selfing"] if selfs else [])):
                 out[(ri, c)] = None
                 continue
             lbf = np.zeros(len(rows))
             for k, row in enumerate(rows[:-1]):
+                if row[0] == row[1]:
+                    lbf[k] = z[(ri, c, "selfing")][plan.selfed[plan.ploidy[c]].index(row[0])] - ln
+                    continue
                 shape, i, j = plan.where(c, row)
                 lbf[k] = z[(ri, c, shape)][i, j] - ln
             out[(ri, c)] = lbf
@@ -2265,18 +2479,22 @@ class Parentage:
     left out of all of them and counted in SKIPPED --, so the rows compare: the table lists them best first, with DELTA the log
     Bayes factor against the best.  A record with a single haplotype, and a progeny without reads at a record, add exactly 0 to
     every row and are counted in RECORDS.  The candidates are called from their own reads alone and enter record by record as
-    independent plug-in posteriors: no selfings, no double reduction, no linkage between the records.
+    independent plug-in posteriors: no double reduction, no linkage between the records.  selfings=True adds, for every candidate
+    of twice the progeny's gamete size, the row (i, i) of a SELF of that candidate -- PARENT_1 and PARENT_2 both carry its name --,
+    listed after the pairs: its two gametes are two meioses of one genotype drawn from the candidate's posterior (selfing_prior), not
+    the plug-in product of the candidate's gamete table with itself.
 
     samples: the source's; candidates: sample names, in the order their pairs are listed in; progeny: sample names, or None for
     every sample that is not a candidate (a sample may be both); gamete_error: one value in [0, 1] for every candidate; top: the
     rows kept per progeny (0: all); frequency_source: as ModelEvidence; budget: the device bytes a launch may take (None: a
-    share of the free memory)."""
+    share of the free memory); selfings: the selfing rows (the '#' line then ends with '; selfings: yes')."""
 
     HEADER = ("PROGENY", "PARENT_1", "PARENT_2", "RECORDS", "SKIPPED", "LOG_BF", "DELTA", "RANK")
 
     def __init__(self, samples, candidates, progeny=None, gamete_error=0.01, top=0, frequency_source="flat",
-                 program="mchap_amd call-exact", budget=None):
+                 program="mchap_amd call-exact", budget=None, selfings=False):
         self.samples = list(samples)
+        self.selfings = bool(selfings)
         self.candidates = list(candidates)
         self.progeny = None if progeny is None else list(progeny)
         self.gamete_error, self.top = float(gamete_error), int(top)
@@ -2293,7 +2511,7 @@ class Parentage:
         """The run's ParentagePlan, formed and checked once; a progeny that no hypothesis but ('.', '.') fits is named on stderr."""
         import sys
 
-        plan = ParentagePlan(self.samples, self.candidates, self.progeny, ploidy_of)
+        plan = ParentagePlan(self.samples, self.candidates, self.progeny, ploidy_of, selfings=self.selfings)
         if self.plan is None:
             self.plan = plan
             for c in plan.progeny:
@@ -2314,9 +2532,11 @@ class Parentage:
         plan = self.resolve(ploidy_of)
         self.records_seen += len(units)
         if backend is not None:
-            got = parentage_host(units, self.samples, ploidy_of, inbreeding_of, plan, self.gamete_error, backend, self.budget)
+            got = parentage_host(units, self.samples, ploidy_of, inbreeding_of, plan, self.gamete_error, backend, self.budget,
+                                 selfings=self.selfings)
         else:
-            got = _parentage_device(units, self.samples, ploidy_of, inbreeding_of, plan, self.gamete_error, self.budget)
+            got = _parentage_device(units, self.samples, ploidy_of, inbreeding_of, plan, self.gamete_error, self.budget,
+                                    selfings=self.selfings)
         for ri, unit in enumerate(units):
             for c in plan.progeny:
                 if (ri, c) in got:
@@ -2345,8 +2565,9 @@ class Parentage:
         return rows
 
     def text(self):
-        lines = ["# %s parentage; frequencies: %s; gamete error: %g; records: %d"
-                 % (self.program, self.frequency_source, self.gamete_error, self.records_seen), "\t".join(self.HEADER)]
+        lines = ["# %s parentage; frequencies: %s; gamete error: %g; records: %d%s"
+                 % (self.program, self.frequency_source, self.gamete_error, self.records_seen, "; selfings: yes" if self.selfings else ""),
+                 "\t".join(self.HEADER)]
         for r in self.table():
             lines.append("\t".join([r["progeny"], r["parent_1"], r["parent_2"], "%d" % r["records"], "%d" % r["skipped"],
                                     "%.6f" % r["log_bf"], "%.6f" % r["delta"], "%d" % r["rank"]]))

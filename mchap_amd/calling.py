@@ -258,6 +258,31 @@ def cross_genotype_prior(parent_posteriors_p, ploidy_p, parent_posteriors_q, plo
     return torch.exp(log_x)[0].cpu().numpy()
 
 
+def selfing_genotype_prior(parent_posteriors, ploidy, n_alleles, gamete_error=0, frequencies=None):
+    """The distribution S float64 [G] of the progeny of a SELFED parent over the genotypes of its own ploidy (not a reference
+    function; the definition: application.selfing_prior): parent_posteriors the parent's genotype posterior [G] in VCF order -- or
+    [n, G] for n parents of one record, and then [n, G] comes back --, an even ploidy, n_alleles haplotypes; gamete_error mixes the
+    multinomial of `frequencies` [n_alleles] (None: flat) into each of the two gametes.  The two gametes come from ONE genotype: unless
+    the posterior is one-hot this is not cross_genotype_prior of the parent with itself.  Its logarithm feeds
+    cross_genotype_posteriors unchanged.  A posterior with a NaN gives NaN throughout, as the definition does.  No double reduction."""
+    import torch
+
+    from .device import ExactSelfing
+
+    H = int(n_alleles)
+    fr = np.full((1, H), 1.0 / H) if frequencies is None else np.asarray(frequencies, dtype=np.float64).reshape(1, H)
+    post = np.ascontiguousarray(parent_posteriors, dtype=np.float64)
+    one = post.ndim == 1
+    post = np.atleast_2d(post)
+    dev = ExactSelfing()
+    with np.errstate(divide="ignore"):
+        # (the posterior itself as the likelihood under the flat genotype prior: the kernel's p is the given one again)
+        llk = torch.from_numpy(np.log(post)).to(dev.device).reshape(-1)
+    S = dev.selfing_prior(llk, H, int(ploidy), None, [0] * len(post), fr, float(gamete_error))[1].cpu().numpy()
+    S[np.any(np.isnan(post), axis=1)] = np.nan   # (the kernel counts a NaN likelihood as 0: the definition gives NaN throughout)
+    return S[0] if one else S
+
+
 def cross_genotype_posteriors(llks, log_cross_prior):
     """The posterior float64 [G_c] of a progeny with log likelihoods llks [G_c] under the log cross prior [G_c]
     (log of cross_genotype_prior): exp(llks + log_cross_prior - log Z).  NaN where no genotype has a finite term."""

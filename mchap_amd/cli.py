@@ -19,8 +19,9 @@ SNV-level VCF `atomize` would make of the run's output with GQ, DS and ACP from 
 depth of every allele (application.AlleleDepths), and `call-exact --cross-calls FILE --cross-parents P Q`, which writes the run's VCF
 again with the progeny of that cross called under their parents' cross prior (application.CrossCalls), and `call-exact --family-calls
 FILE --cross-parents P Q`, which writes it with the parents and the progeny called jointly (application.FamilyCalls), and `call-exact
---parentage FILE --parentage-candidates A B ... [--parentage-progeny C ...] [--parentage-gamete-error E] [--parentage-top N]`, which
-writes a table that ranks every pair of candidate parents per progeny (application.Parentage), and `call-exact --identity FILE
+--parentage FILE --parentage-candidates A B ... [--parentage-progeny C ...] [--parentage-gamete-error E] [--parentage-top N]
+[--parentage-selfings]`, which writes a table that ranks every pair of candidate parents per progeny -- with --parentage-selfings every
+self of a candidate too -- (application.Parentage), and `call-exact --identity FILE
 [--identity-samples A B ...] [--identity-error E] [--identity-min-log-bf X]`, which writes a table that ranks the pairs of samples
 by the evidence that they are one individual (application.Identity).  `atomize --haplotypes FILE` is host only (mchap_amd/atomize.py)."""
 import argparse
@@ -202,6 +203,9 @@ def build_parser(program):
                                 "not from its parent, one value in [0, 1] for every candidate (default: 0.01)")
             p.add_argument("--parentage-top", type=int, nargs=1, default=[None], metavar="N",
                            help="(not a reference flag) with --parentage: keep the first N rows of every progeny (default 0: all)")
+            p.add_argument("--parentage-selfings", action="store_true",
+                           help="(not a reference flag) with --parentage: also rank, per progeny, the self (i, i) of every candidate of "
+                                "the progeny's ploidy -- two meioses of one genotype drawn from the candidate's posterior")
             p.add_argument("--identity", type=str, nargs=1, default=[None], metavar="FILE",
                            help="(not a reference flag) write to FILE, when the run ends, a table that ranks the pairs of samples of one "
                                 "ploidy and one calling prior by the log Bayes factor of 'one genotype, read twice' against unrelated, "
@@ -389,6 +393,8 @@ CROSS_FLAGS = ("--cross-calls", "--cross-parents", "--cross-progeny", "--gamete-
 FAMILY_FLAGS = ("--family-calls",)
 # ... and the flags of the parentage table
 PARENTAGE_FLAGS = ("--parentage", "--parentage-candidates", "--parentage-progeny", "--parentage-gamete-error", "--parentage-top")
+# ... and the flag of its selfing rows, in a tuple of its own
+PARENTAGE_SELFING_FLAGS = ("--parentage-selfings",)
 # ... and the flags of the identity table
 IDENTITY_FLAGS = ("--identity", "--identity-samples", "--identity-error", "--identity-min-log-bf")
 
@@ -403,7 +409,7 @@ def _header_argv(argv, options):
             name = a.split("=", 1)[0]
             full = [name] if name in options else [o for o in options if o.startswith(name)]
             skipping = len(full) == 1 and full[0] in EVIDENCE_FLAGS + SNV_FLAGS + ALLELE_DEPTH_FLAGS + CROSS_FLAGS + FAMILY_FLAGS + PARENTAGE_FLAGS + \
-                IDENTITY_FLAGS
+                PARENTAGE_SELFING_FLAGS + IDENTITY_FLAGS
         if not skipping:
             out.append(a)
     return out
@@ -532,12 +538,15 @@ def identity_settings(args, samples, ploidy, inbreeding, tag, estimate, world):
 def parentage_settings(args, samples, ploidy, inbreeding, tag, estimate, world):
     """The --parentage / --parentage-* flags of call-exact -> an application.Parentage, or None without --parentage (any
     --parentage-* flag is then an error).  The hypotheses are checked here, before any work: the sample names, none twice, every
-    candidate of even ploidy, the gamete error in [0, 1], N >= 0."""
+    candidate of even ploidy, the gamete error in [0, 1], N >= 0.  --parentage-selfings (read with getattr: a namespace built by hand
+    may lack it) adds the selfing rows."""
     from . import application
 
+    selfings = bool(getattr(args, "parentage_selfings", False))
     if args.parentage[0] is None:
         for flag, value in (("--parentage-candidates", args.parentage_candidates), ("--parentage-progeny", args.parentage_progeny),
-                            ("--parentage-gamete-error", args.parentage_gamete_error[0]), ("--parentage-top", args.parentage_top[0])):
+                            ("--parentage-gamete-error", args.parentage_gamete_error[0]), ("--parentage-top", args.parentage_top[0]),
+                            ("--parentage-selfings", True if selfings else None)):
             if value is not None:
                 raise ValueError("%s needs --parentage" % flag)
         return None
@@ -552,7 +561,8 @@ def parentage_settings(args, samples, ploidy, inbreeding, tag, estimate, world):
     if top < 0:
         raise ValueError("--parentage-top: N >= 0")
     source = "estimated" if estimate is not None else ("flat" if (tag is None or inbreeding is None) else "tag %s" % tag)
-    table = application.Parentage(samples, args.parentage_candidates, args.parentage_progeny, error, top, frequency_source=source)
+    table = application.Parentage(samples, args.parentage_candidates, args.parentage_progeny, error, top, frequency_source=source,
+                                  selfings=selfings)
     table.resolve(application._per_sample(ploidy, samples))
     return table
 

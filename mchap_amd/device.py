@@ -1097,6 +1097,105 @@ class ExactParentage:
         return out
 
 
+class ExactSelfing:
+    """Selfed parents per progeny for exact-caller units whose likelihoods are resident on the device
+    (mchap_exact_selfing_prior_device, mchap_exact_selfing_evidence_device): the genotype prior of a progeny whose two gametes are
+    two meioses of one genotype drawn from a candidate's posterior, and the evidence of every progeny of a record under every
+    candidate's such prior.  The definitions: application.selfing_prior, application.selfing_evidence."""
+
+    def __init__(self, device=None):
+        self.torch = _torch()
+        self.device = _device(self.torch, device)
+        self.launches = 0      # calls enqueued
+
+    _tensor = ExactModelEvidence._tensor
+    _prior = ExactCross._prior
+
+    @staticmethod
+    def prior_workspace_bytes(n_units, n_haps, ploidy):
+        """The bytes of workspace a selfing_prior call needs, or -1 for a shape the kernels refuse."""
+        return int(_lib.lib().mchap_exact_selfing_prior_workspace_bytes(int(n_units), int(n_haps), int(ploidy)))
+
+    @staticmethod
+    def evidence_workspace_bytes(n_records, n_progeny, n_candidates, n_haps, ploidy):
+        """The bytes of workspace a log_evidence call needs, or -1 for a shape the kernels refuse."""
+        return int(_lib.lib().mchap_exact_selfing_evidence_workspace_bytes(int(n_records), int(n_progeny), int(n_candidates),
+                                                                           int(n_haps), int(ploidy)))
+
+    def selfing_prior(self, llks64, n_haps, ploidy, inbreeding, unit_row, freqs, gamete_error, workspace_limit=None):
+        """The selfing priors of candidate units of one shape (n_haps, even ploidy), enqueued on torch's current stream; the
+        arguments are ExactCross.gametes': llks64 a float64 tensor [U * G] on the device; inbreeding [U] (or a scalar), every F in
+        [0, 1), or None: the flat genotype prior; unit_row [U]: each unit's row of freqs [rows, stride >= n_haps]; gamete_error [U]
+        (or a scalar), every e in [0, 1].  F and e are checked here, on the host copies.  Returns float64 tensors on the device:
+        (log_self [U, G], self_prior [U, G], log_norm [U]) -- log S, S and the unit's normaliser --, NaN rows for a unit without a
+        finite genotype.  A shape the library refuses, or a workspace beyond workspace_limit bytes (None: what the device has
+        free): NotImplementedError."""
+        torch, dev = self.torch, self.device
+        H, K = int(n_haps), int(ploidy)
+        G = ExactCross._shape(H, K)
+        if K % 2:
+            raise ValueError("selfing_prior: a parent of odd ploidy %d" % K)
+        assert llks64.dtype == torch.float64 and llks64.is_contiguous() and llks64.numel() % G == 0
+        U = llks64.numel() // G
+        e = np.array(np.broadcast_to(np.asarray(gamete_error, dtype=np.float64), (U,)))
+        if not np.all((e >= 0.0) & (e <= 1.0)):
+            raise ValueError("gamete_error: every e must lie in [0, 1]")
+        d_F, d_row, d_fr, stride = self._prior(U, H, inbreeding, unit_row, freqs)
+        log_self, lin = (torch.empty((U, G), dtype=torch.float64, device=dev) for _ in range(2))
+        norm = torch.empty(U, dtype=torch.float64, device=dev)
+        if U == 0:
+            return log_self, lin, norm
+        wsb = self.prior_workspace_bytes(U, H, K)
+        limit = workspace_limit
+        if limit is None:
+            limit, _ = torch.cuda.mem_get_info()
+        if wsb < 0 or wsb > limit:
+            raise NotImplementedError("mchap_hip: selfing prior of %d units of ploidy %d over %d haplotypes: the shape is refused, "
+                                      "or its workspace does not fit the device" % (U, K, H))
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+        d_e = torch.from_numpy(e).to(dev)
+        _lib.check(_lib.lib().mchap_exact_selfing_prior_device(
+            U, _ptr(llks64), H, K, _ptr(d_F), _ptr(d_row), _ptr(d_fr), stride, _ptr(d_e), _ptr(log_self), _ptr(lin), _ptr(norm),
+            _ptr(ws), C.c_int64(wsb), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        self.launches += 1
+        return log_self, lin, norm
+
+    def log_evidence(self, self_prior, llks_c, n_haps, ploidy, progeny_reads=None, workspace_limit=None):
+        """The records of one shape, enqueued on torch's current stream: self_prior [R, n, G] the candidates' selfing priors (S, a
+        float64 tensor on the device), llks_c [R * C * G] the progeny's likelihoods, progeny_reads [R, C] of 0 / 1 (None: every
+        progeny has reads).  workspace_limit: the bytes the caller offers (None: what the device has free); a workspace beyond
+        it, or a shape the library refuses: NotImplementedError.  Returns log_z [R, C, n] on the device."""
+        torch, dev = self.torch, self.device
+        H, K = int(n_haps), int(ploidy)
+        G = ExactCross._shape(H, K)
+        assert self_prior.dtype == torch.float64 and self_prior.is_contiguous() and self_prior.dim() == 3
+        R, n = int(self_prior.shape[0]), int(self_prior.shape[1])
+        assert int(self_prior.shape[2]) == G and n >= 1
+        assert llks_c.dtype == torch.float64 and llks_c.is_contiguous() and (R == 0 or llks_c.numel() % (R * G) == 0)
+        Cn = llks_c.numel() // (R * G) if R else 0
+        d_reads = None
+        if progeny_reads is not None:
+            reads = np.ascontiguousarray(progeny_reads, dtype=np.int32)
+            assert reads.shape == (R, Cn)
+            d_reads = torch.from_numpy(reads).to(dev)
+        out = torch.empty((R, Cn, n), dtype=torch.float64, device=dev)
+        if R == 0 or Cn == 0:
+            return out
+        wsb = self.evidence_workspace_bytes(R, Cn, n, H, K)
+        limit = workspace_limit
+        if limit is None:
+            limit, _ = torch.cuda.mem_get_info()
+        if wsb < 0 or wsb > limit:
+            raise NotImplementedError("mchap_hip: selfing evidence of %d records x %d progeny x %d candidates over %d haplotypes: the "
+                                      "shape is refused, or its workspace does not fit the device" % (R, Cn, n, H))
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().mchap_exact_selfing_evidence_device(
+            R, Cn, n, _ptr(self_prior), _ptr(llks_c), _ptr(d_reads), H, K, _ptr(out), _ptr(ws), C.c_int64(wsb),
+            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        self.launches += 1
+        return out
+
+
 class ExactIdentity:
     """Sample pairs by shared-genotype evidence for exact-caller units whose likelihoods are resident on the device
     (mchap_exact_identity_device): per record the log Bayes factor of "one genotype read twice" against two independent draws
